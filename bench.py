@@ -20,6 +20,11 @@ says so); the slice GEMM alone is the side key ``kernel_only``.  Token-parallel 
 rank its own 4096 tokens) are a side key (``replicas``, weak scaling), config C5 hidden-dim
 sharded over RCCL is ``denoise_loop_tp`` and C5 token-parallel (each rank its 2048 / N tokens of
 the sample, replicated weights) ``denoise_loop_dp``.
+
+A plain run (``--gpus N --steps S --warmup W``) sets up, warms up, times the S headline steps, writes
+the last step's Y with ``--dump-outputs DIR`` and prints the JSON line.  Every side key named above
+and below (``f16_weights``, ``denoise_loop*``, ``replicas``, ``kernel_only`` and the N > 1
+``roofline``, ``m_sweep``, ``cpu_baseline``) is a run of its own and is measured with ``--full`` only.
 """
 from __future__ import annotations
 
@@ -55,9 +60,16 @@ def parse():
     p.add_argument("--N", type=int, default=4096)
     p.add_argument("--bits", type=int, default=4)
     p.add_argument("--group", type=int, default=128)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's output as DIR/Y.npy (float32; a fixed "
+                        "seeded sample of its rows when the whole Y is over the size cap)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the side measurements (f16_weights, denoise_loop*, replicas, kernel_only, "
+                        "cpu_baseline, --sweep); a plain run times the headline step only")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
-    p.add_argument("--no-cpu", action="store_true")
-    p.add_argument("--sweep", action="store_true", help="rank 0 at N = 1: add the local layer's M-sweep (m_sweep) to the JSON line")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
+    p.add_argument("--sweep", action="store_true",
+                   help="--full, rank 0 at N = 1: add the local layer's M-sweep (m_sweep) to the JSON line")
     p.add_argument("--tp-steps", type=int, default=10,
                    help="N > 1: steps of the hidden-dim-sharded C5 loop reported as 'denoise_loop_tp' (0 skips)")
     p.add_argument("--dp-steps", type=int, default=50,
@@ -66,11 +78,13 @@ def parse():
                    help="N > 1: token chunks of the headline step's all-gather (chunk i's gather overlaps "
                         "chunk i+1's GEMM; 2 by default: priced in DESIGN.md section 6)")
     p.add_argument("--no-denoise", action="store_true",
-                   help="skip the config-C5 denoise-loop side measurement (reported as 'denoise_loop')")
+                   help="--full: skip the config-C5 denoise-loop side measurement (reported as 'denoise_loop')")
     p.add_argument("--prewarm-ms", type=float, default=300.0,
                    help="untimed launches of the same step before the W warmup steps, so the clocks "
                         "have ramped before timing (outside the timed region)")
     a = p.parse_args()
+    if a.sweep and not a.full:
+        p.error("--sweep is a side measurement: add --full")
     for name in ("tp_steps", "dp_steps"):
         if getattr(a, name) == 1:
             # a 1-step schedule is the reference's degenerate linear schedule (0/0 in the beta ramp,
@@ -374,11 +388,13 @@ def headline(world, M, steps, t_slice, t_full=None, chunks=1):
         return {"value": M * steps / t_slice, "ms_per_step": t_slice / steps * 1e3, "value_from": "gemm"}
     if t_full is None:
         raise ValueError("N > 1: the headline needs the gathered step's time")
-    return {"value": M * steps / t_full, "ms_per_step": t_full / steps * 1e3,
-            "value_from": f"gemm+allgather (chunks={chunks})",
-            "kernel_only": {"value": round(M * steps / t_slice, 1), "ms_per_step": round(t_slice / steps * 1e3, 5),
-                            "note": "the rank's column-slice GEMM alone (kernel only: the full Y exists on no "
-                                    "rank; not the headline)"}}
+    head = {"value": M * steps / t_full, "ms_per_step": t_full / steps * 1e3,
+            "value_from": f"gemm+allgather (chunks={chunks})"}
+    if t_slice is not None:   # timed with --full only
+        head["kernel_only"] = {"value": round(M * steps / t_slice, 1), "ms_per_step": round(t_slice / steps * 1e3, 5),
+                               "note": "the rank's column-slice GEMM alone (kernel only: the full Y exists on no "
+                                       "rank; not the headline)"}
+    return head
 
 
 def _timed(fn, steps, stream, torch, dist, world, dev):
@@ -451,6 +467,25 @@ def m_sweep(lin, K, N, bits, group, torch, dev, stream, n_layers=40):
     for lyr in chain:
         lyr.close()
     return {"layers": n_layers, "timing": "HIP graph replay, HIP events", "rows": rows}
+
+
+DUMP_CAP_BYTES = 32 * 2**20   # per dumped array, as float32
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: ``arrays`` (name -> 2-D device tensor the timed step returned) as
+    DIR/<name>.npy in float32.  An array over DUMP_CAP_BYTES is cut to a fixed sample of its rows
+    (sorted, drawn without replacement by numpy's default_rng(0) from the row count alone), so two
+    builds run with the same arguments write the same rows of the same seeded inputs."""
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        rows, row_bytes = t.shape[0], 4 * t.shape[1]
+        keep = max(1, DUMP_CAP_BYTES // row_bytes)
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+            t = t[idx.tolist()]
+        np.save(out / f"{name}.npy", t.float().cpu().numpy())
 
 
 def _free_port():
@@ -559,9 +594,10 @@ def main():
     for _ in range(args.warmup):
         step()
     # the rank's slice GEMM alone: the roofline kernel (HIP events on its stream); at N = 1 this IS
-    # the step
-    t_slice, kernel_ms = _timed(step, args.steps, stream, torch, dist, world, dev)
-    t_full = None
+    # the step, at N > 1 a side figure (kernel_only, roofline) timed with --full only
+    t_slice = kernel_ms = t_full = None
+    if world == 1 or args.full:
+        t_slice, kernel_ms = _timed(step, args.steps, stream, torch, dist, world, dev)
     if world > 1:
         # the whole step on every rank: Y = x.dot(W) + b as the full [M, N] (lib.rs:806-813) = the
         # rank's column-slice GEMM + the RCCL all-gather of the f16 slices into Y's rows
@@ -574,14 +610,25 @@ def main():
         for _ in range(max(2, args.warmup)):
             step_full()
         t_full, _ = _timed(step_full, args.steps, stream, torch, dist, world, dev)
+    if args.dump_outputs and rank == 0:
+        # what the timed step's caller holds after the last step, before any side measurement reuses Y
+        dump_outputs(args.dump_outputs, {"Y": Y if world == 1 else Yfull})
     head = headline(world, M, args.steps, t_slice, t_full, args.gather_chunks)
     value, ms_per_step = head["value"], head["ms_per_step"]
 
     flops_local = 2.0 * M * n_local * K
-    abytes_local = algorithmic_bytes(M, K, n_local, args.bits, args.group)
-    achieved_tflops = flops_local / (kernel_ms * 1e-3) / 1e12
-    pmc_cfg = {"M": M, "K": K, "N_local": n_local, "bits": args.bits, "group": args.group, "rev": GEMM_REV}
-    pmc = load_pmc_traffic(pmc_cfg)
+    roofline = None
+    if kernel_ms is not None:
+        abytes_local = algorithmic_bytes(M, K, n_local, args.bits, args.group)
+        achieved_tflops = flops_local / (kernel_ms * 1e-3) / 1e12
+        pmc_cfg = {"M": M, "K": K, "N_local": n_local, "bits": args.bits, "group": args.group, "rev": GEMM_REV}
+        pmc = load_pmc_traffic(pmc_cfg)
+        roofline = {"bound": "mfma", "achieved": round(achieved_tflops, 1), "peak": PEAK_F16_TFLOPS,
+                    "unit": "TFLOP/s", "frac": round(achieved_tflops / PEAK_F16_TFLOPS, 4),
+                    "traffic": None if pmc is None else pmc[0],
+                    "traffic_source": None if pmc is None else pmc[1],
+                    "algorithmic_bytes": abytes_local, "kernel_ms": round(kernel_ms, 5),
+                    "kernel": f"rank 0's local GEMM, M={M} x K={K} x N={n_local}"}
     out = {
         "metric": "int4 dequant+GEMM GiB/s & tok/s per denoise step, 4096×4096, 1/2/4/8 GPU",
         "value": round(value, 1), "unit": "tok/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -598,15 +645,26 @@ def main():
         "value_from": head["value_from"],
         "gib_per_s": round(algorithmic_bytes(M, K, N, args.bits, args.group) / (ms_per_step * 1e-3) / 2**30, 1),
         "tflops": round(2.0 * M * N * K / (ms_per_step * 1e-3) / 1e12, 1),
-        "roofline": {"bound": "mfma", "achieved": round(achieved_tflops, 1), "peak": PEAK_F16_TFLOPS,
-                     "unit": "TFLOP/s", "frac": round(achieved_tflops / PEAK_F16_TFLOPS, 4),
-                     "traffic": None if pmc is None else pmc[0],
-                     "traffic_source": None if pmc is None else pmc[1],
-                     "algorithmic_bytes": abytes_local, "kernel_ms": round(kernel_ms, 5),
-                     "kernel": f"rank 0's local GEMM, M={M} x K={K} x N={n_local}"},
+        "roofline": roofline,
     }
+    if roofline is None:
+        del out["roofline"]
     if "kernel_only" in head:
         out["kernel_only"] = head["kernel_only"]
+    if args.full:
+        side_measurements(out, args, d, torch, dist, dev, world, rank, lin, W, X, Y, stream)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    lin.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def side_measurements(out, args, d, torch, dist, dev, world, rank, lin, W, X, Y, stream):
+    """--full: everything the JSON line carries beside the headline step, each a run of its own
+    (replicas, f16_weights, denoise_loop*, m_sweep, cpu_baseline), added to ``out``."""
+    M, K, N = args.M, args.K, args.N
+    flops_local = 2.0 * M * Y.shape[1] * K
     if world > 1:
         full = d.QuantLinear.from_weight(W, None, args.bits, args.group)
         Yf = torch.empty(M, N, dtype=torch.float16, device=dev)
@@ -629,7 +687,6 @@ def main():
                               "note": "DLLM_PRECISION_F16W: weight rounded to f16 before the MFMA (~2.7e-4 "
                                       "more relative error per layer); kernel time only"}
         lin16.close()
-    del W
     if not args.no_denoise:
         out["denoise_loop"] = denoise_loop(d, torch, dev)
         if world > 1 and args.tp_steps > 0:
@@ -644,11 +701,6 @@ def main():
         out["cpu_baseline"] = cpu_baseline(K, N, args.bits, args.group, M, args.cpu_seconds)
         if "denoise_loop" in out:
             out["denoise_loop"]["cpu_baseline"] = cpu_denoise_step()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    lin.close()
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

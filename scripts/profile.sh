@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT="$PWD/gpurun_out/prof"
 mkdir -p "$OUT"
-BARGS="${BENCH_ARGS:---steps 20 --warmup 5 --no-cpu}"
+BARGS="${BENCH_ARGS:---steps 20 --warmup 5 --full --no-cpu}"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv -- python3 bench.py $BARGS > "$OUT/kt.log" 2>&1
 rc=$?; echo "kernel-trace rc=$rc"; tail -3 "$OUT/kt.log"
 [ $rc -eq 0 ] || exit $rc

@@ -68,6 +68,36 @@ def test_spawn_ranks_stops_blocked_rank0_when_rank1_fails(tmp_path):
     assert __import__("time").perf_counter() - t0 < 30
 
 
+def test_sweep_is_refused_without_full():
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--sweep"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
+def test_dump_outputs_writes_f32_and_a_fixed_row_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a small Y is written whole as float32; one over the cap is cut to the same
+    sorted row sample on every call (a function of the row count only)."""
+    import numpy as np
+    import torch
+    y = torch.arange(40 * 8, dtype=torch.float32).reshape(40, 8).half()
+    bench.dump_outputs(tmp_path / "a" / "b", {"Y": y})
+    whole = np.load(tmp_path / "a" / "b" / "Y.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, y.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 10 * 8 * 4)       # room for 10 of the 40 rows
+    bench.dump_outputs(tmp_path / "c", {"Y": y})
+    bench.dump_outputs(tmp_path / "d", {"Y": y})
+    cut = np.load(tmp_path / "c" / "Y.npy")
+    assert cut.shape == (10, 8) and cut.dtype == np.float32
+    assert np.array_equal(cut, np.load(tmp_path / "d" / "Y.npy"))
+    rows = (cut[:, 0] / 8).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(cut, whole[rows])
+
+
+def test_headline_without_slice_time_has_no_kernel_only():
+    """A plain N > 1 run times the gathered step only: no ``kernel_only`` key."""
+    h = bench.headline(4, 4096, 10, t_slice=None, t_full=0.9e-3, chunks=2)
+    assert h["value"] == 4096 * 10 / 0.9e-3 and "kernel_only" not in h
+
+
 def test_headline_value_is_the_whole_step_at_n_gt_1():
     """N > 1: ``value`` comes from the gathered step (slice GEMM + all-gather, the full Y on every
     rank), never from the slice GEMM alone, which stays the side key ``kernel_only``."""
