@@ -68,6 +68,27 @@ _ERRORS = {ERR_INVALID_PARAMS: InvalidParams, ERR_UNSUPPORTED: UnsupportedOperat
            ERR_SHAPE_MISMATCH: ShapeMismatch, ERR_CALIBRATION_REQUIRED: CalibrationRequired,
            ERR_SERIALIZATION: SerializationError, ERR_HIP: HipError, ERR_NO_DEVICE: HipError}
 
+# enum dllm_linear_kernel / dllm_linear_plan_flags (dllm_linear_plan, dllm_linear_plan_shape).
+KERNEL_DECODE, KERNEL_HORNER16, KERNEL_HORNER_PC, KERNEL_HORNER_KG2, KERNEL_HORNER_PC_KG2, KERNEL_EXACT_FOLD, \
+    KERNEL_ROUNDED_RING = range(1, 8)
+KERNEL_NAMES = {KERNEL_DECODE: "DECODE", KERNEL_HORNER16: "HORNER16", KERNEL_HORNER_PC: "HORNER_PC",
+                KERNEL_HORNER_KG2: "HORNER_KG2", KERNEL_HORNER_PC_KG2: "HORNER_PC_KG2",
+                KERNEL_EXACT_FOLD: "EXACT_FOLD", KERNEL_ROUNDED_RING: "ROUNDED_RING"}
+PLAN_STAGGERED, PLAN_DECODE_XL, PLAN_SPLITK, PLAN_NOT_FUSED = 1, 2, 4, 8
+
+
+class LinearPlan(C.Structure):
+    """dllm_linear_plan_t: the kernel and tiles one forward launches."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "tile_m", "tile_n", "kgroups", "nsplit", "flags")]
+
+    def astuple(self):
+        return (KERNEL_NAMES.get(self.kernel, self.kernel), self.tile_m, self.tile_n, self.kgroups, self.nsplit,
+                self.flags)
+
+    def __repr__(self):
+        return "LinearPlan(kernel=%s, tile=%dx%d, kgroups=%d, nsplit=%d, flags=%d)" % self.astuple()
+
+
 P, S, U8, I32, U32, FL, INT = (C.c_void_p, C.c_size_t, C.c_uint8, C.c_int32, C.c_uint32, C.c_float, C.c_int)
 U64 = C.c_uint64
 
@@ -116,6 +137,8 @@ SIGNATURES = {
     "dllm_linear_create_ex": (INT, [P, P, S, S, U8, S, INT, P, P]),
     "dllm_linear_create_quantized_ex": (INT, [P, P, P, P, S, S, U8, S, INT, P, P]),
     "dllm_linear_precision": (INT, [P]),
+    "dllm_linear_plan": (INT, [P, S, INT, P]),
+    "dllm_linear_plan_shape": (INT, [S, S, U8, S, INT, INT, S, INT, P]),
     "dllm_linear_destroy": (INT, [P]),
     "dllm_kv_attention": (INT, [P, P, P, P, P, U8, S, S, S, P, P]),
     "dllm_beta_schedule": (INT, [INT, S, FL, FL, P]),
@@ -191,6 +214,16 @@ def use(path: str | os.PathLike):
     global _lib
     _lib = load(path)
     return _lib
+
+
+def linear_plan_shape(K: int, N: int, bits: int, group: int, M: int, *, precision: int = 0, prefill_only: bool = False,
+                      horner_ok: bool = True, fused: bool = False) -> LinearPlan:
+    """dllm_linear_plan_shape: the plan of an M-row forward of a [K, N] layer, without a handle or a
+    device (host arithmetic only)."""
+    plan = LinearPlan()
+    check(load().dllm_linear_plan_shape(K, N, bits, group, int(precision) | (0x100 if prefill_only else 0),
+                                        int(bool(horner_ok)), M, int(bool(fused)), C.byref(plan)))
+    return plan
 
 
 def check(rc: int):

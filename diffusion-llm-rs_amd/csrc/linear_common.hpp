@@ -335,6 +335,10 @@ struct ExactGemmArgs {
     const float *hr = nullptr;   // Horner ratios (DLLM_EXACT_HORNER builds: the 128 x 256 tiles in Horner form)
 };
 int launch_exact_gemm(const ExactGemmArgs &a, int y_f32, hipStream_t st);
+// The fold-form tile selection (the one routine launch_exact_gemm switches on and dllm_linear_plan
+// reports): fills tile_m, tile_n, kgroups, nsplit and flags of a DLLM_KERNEL_EXACT_FOLD plan.  Host
+// arithmetic only.  Needs exact_gemm_supported(M, K, Npad, group).
+void select_exact_plan(int bits, int M, int K, int Npad, int group, dllm_linear_plan_t *p);
 
 // Exact-weight int4 g128 GEMM in Horner form on 256 x 256 tiles (linear_horner.hip): hr = the
 // handle's ratios [G + 1][Npad], sf = its f32 scales (the last group's multiply the result).

@@ -1065,14 +1065,117 @@ constexpr int kMidRing = 3;
 #define DLLM_MIDM_MINFILL 48
 #endif
 
-template <int BITS, typename YT, int G64, int EPI>
-int launch_exact_bits(const ExactGemmArgs &a, hipStream_t st) {
-    const int mb = (a.M + 127) / 128;
+// The product selection above as one host routine (select_exact_plan, below the namespace) that
+// launch_exact_bits switches on; the template arguments each plan maps to are the launcher's.
+inline void exact_plan(int bits, int M, int K, int Npad, int group, dllm_linear_plan_t *p) {
+    const int g64 = group / kBK, mb = (M + 127) / 128;
+    // the int4 g128 forms: weight words in registers (WREG)
+    const bool i4g128 = g64 == 2 && bits == 4 && DLLM_EXACT_WREG;
+    auto set = [&](int tm, int tn, int kg, int ns, int flags) {
+        p->kernel = DLLM_KERNEL_EXACT_FOLD;
+        p->tile_m = tm; p->tile_n = tn; p->kgroups = kg; p->nsplit = ns;
+        p->flags = flags | (ns > 1 ? DLLM_PLAN_SPLITK : 0);
+    };
+    if (Npad % 256 == 0 && mb * (Npad / 256) >= kCUs) {
+        const bool stag = DLLM_EXACT_STAG && i4g128 && !DLLM_EXACT_S16 && !DLLM_EXACT_RING2 && !DLLM_EXACT_HORNER;
+        return set(128, 256, 1, 1, stag ? DLLM_PLAN_STAGGERED : 0);
+    }
+    const int tiles = mb * (Npad / 128), ngroups = K / group;
+    const int t64 = ((M + 63) / 64) * (Npad / 128);
+    // Mid M (int4 g128): 32 x 128 tiles of 4 waves streaming the whole K -- no K split, hence no
+    // f32 slabs and no combine launch -- where they give a full round but 64 x 128 tiles do not
+    // (M 225..448 at N = 4096, where the policy below splits K): M 256 / 384: 25.1 -> 20.4 /
+    // 30.0 -> 24.6 us; at M >= 512 the 64 x 128 two-k-group tiles stay faster (23.1 vs 25.8 us)
+    // (profiles/r03_midm/policy_ab.json).
+    if (i4g128) {
+        const int t32 = ((M + 31) / 32) * (Npad / 128);
+        if (tiles < kCUs && t64 < kCUs && t32 >= DLLM_MIDM_MINFILL) {
+            // k-groups of 4 waves sharing the tile (k-group g streams the g-th part of K; sums handed
+            // to k-group 0 through the ring): four (16 waves, one block per CU) while the grid is
+            // one block per CU, else two (8 waves, two blocks per CU fit).  M 256: 20.4 (one
+            // k-group) -> 15.5 (two) -> 14.3 us (four); M 384: 24.5 -> 22.1 (two) / 25.1 (four)
+            // (profiles/r03_midm/kgroups.jsonl).
+            if (t32 <= kCUs && ngroups % 4 == 0) return set(32, 128, 4, 1, 0);
+            if (ngroups % 2 == 0) return set(32, 128, 2, 1, 0);
+            return set(32, 128, 1, 1, 0);
+        }
+    }
+    // tile-starved grids: 128 x 128 (or 64 x 128) tiles with two k-groups of 4 waves per block
+    if (DLLM_EXACT_KG2 && i4g128) {
+        if (tiles >= kCUs && tiles < 2 * kCUs && ngroups % 2 == 0) return set(128, 128, 2, 1, 0);
+        if (tiles < kCUs && t64 >= kCUs && ngroups % 2 == 0) return set(64, 128, 2, 1, 0);
+    }
+    if (DLLM_EXACT_MR2 && tiles < 2 * kCUs) {
+        int ns = 1;
+        while (t64 * ns < 2 * kCUs && ns < 8 && ngroups % (2 * ns) == 0 && (K / kBK) / (2 * ns) >= 4) ns *= 2;
+        return set(64, 128, 1, ns, 0);
+    }
+    int nsplit = 1;
+    while (tiles * nsplit < 200 && nsplit < 8 && ngroups % (2 * nsplit) == 0 && (K / kBK) / (2 * nsplit) >= 4)
+        nsplit *= 2;
+    return set(128, 128, 1, nsplit, 0);
+}
+
 #if DLLM_LAB
+// Lab A/B overrides of the tile policy (ExactGemmArgs::tm, lab_policy), applied after the product
+// plan: -1 = no override for this shape (the product plan runs).
+template <int BITS, typename YT, int G64, int EPI>
+int launch_exact_lab(const ExactGemmArgs &a, hipStream_t st) {
+    const int mb = (a.M + 127) / 128;
     if (a.tm && a.Npad % 256 == 0 && ((a.M + 255) / 256) * (a.Npad / 256) >= kCUs)
         return launch_exact_tile<BITS, YT, 8, 8, 1, G64, EPI, true>(a, 1, st);
+    if (a.lab_policy == 0 || (a.Npad % 256 == 0 && mb * (a.Npad / 256) >= kCUs)) return -1;
+    if constexpr (G64 == 2 && BITS == 4 && DLLM_EXACT_WREG) {
+        const int tiles = mb * (a.Npad / 128), ngroups = a.K / a.group;
+        const int t32 = ((a.M + 31) / 32) * (a.Npad / 128), t64 = ((a.M + 63) / 64) * (a.Npad / 128);
+        const bool mid = tiles < kCUs && t64 < kCUs && t32 >= DLLM_MIDM_MINFILL;
+        if (mid) {
+            switch (a.lab_policy) {   // lab A/B: one k-group (RING 3) / two k-groups / four (RING 3)
+            case 2: return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, kMidRing>(a, 1, st);
+            case 3: if (ngroups % 2 == 0) return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
+                    break;
+            case 4: if (ngroups % 4 == 0) return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 3, 4>(a, 1, st);
+                    break;
+            default: break;
+            }
+            if (a.lab_policy != 1) return -1;
+        }
+#if DLLM_EXACT_KG2
+        // (policy 5: 64 x 128 tiles, two blocks per CU, where 128 x 128 tiles give one round;
+        // 6 / 7: the 128 x 128 tiles with 64-deep stages in a 4- / 3-stage ring instead of 128-deep
+        // stages in a 2-stage ring; 1: the round-2 tile policy, no 32 x 128 mid-M tiles)
+        const bool one_round = tiles >= kCUs && tiles < 2 * kCUs && ngroups % 2 == 0;
+        if (one_round && a.lab_policy == 6) return launch_exact_tile<BITS, YT, 4, 4, 1, 2, EPI, false, 1, 4, 2>(a, 1, st);
+        if (one_round && a.lab_policy == 7) return launch_exact_tile<BITS, YT, 4, 4, 1, 2, EPI, false, 1, 3, 2>(a, 1, st);
+        if (one_round && a.lab_policy != 5) return launch_exact_tile<BITS, YT, 4, 4, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
+        if ((tiles < kCUs || a.lab_policy == 5) && t64 >= kCUs && ngroups % 2 == 0)
+            return launch_exact_tile<BITS, YT, 4, 2, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
 #endif
-    if (a.Npad % 256 == 0 && mb * (a.Npad / 256) >= kCUs) {
+#if DLLM_EXACT_MR2
+        if (mid && tiles < 2 * kCUs) {   // policy 1 on a mid-M grid: the K-split 64 x 128 tiles
+            int ns = 1;
+            while (t64 * ns < 2 * kCUs && ns < 8 && ngroups % (2 * ns) == 0 && (a.K / kBK) / (2 * ns) >= 4) ns *= 2;
+            return launch_exact_tile<BITS, YT, 4, 2, 1, G64, EPI>(a, ns, st);
+        }
+#endif
+    }
+    return -1;
+}
+#endif
+
+template <int BITS, typename YT, int G64, int EPI>
+int launch_exact_bits(const ExactGemmArgs &a, hipStream_t st) {
+#if DLLM_LAB
+    if (a.tm || a.lab_policy) {
+        const int rc = launch_exact_lab<BITS, YT, G64, EPI>(a, st);
+        if (rc >= 0) return rc;
+    }
+#endif
+    dllm_linear_plan_t p;
+    exact_plan(BITS, a.M, a.K, a.Npad, a.group, &p);
+    constexpr bool kI4G128 = G64 == 2 && BITS == 4 && DLLM_EXACT_WREG;
+    const int ns = p.nsplit;
+    if (p.tile_m == 128 && p.tile_n == 256) {
         // int8 weights: one-slab stages (two-slab stages exceed the 160 KiB LDS ring)
         if constexpr (G64 == 1 || BITS == 8) return launch_exact_tile<BITS, YT, 8, 4, 1, G64, EPI>(a, 1, st);
 #if DLLM_EXACT_RING2
@@ -1094,67 +1197,25 @@ int launch_exact_bits(const ExactGemmArgs &a, hipStream_t st) {
 #endif
         else return launch_exact_tile<BITS, YT, 8, 4, 2, G64 / 2, EPI>(a, 1, st);
     }
-    const int tiles = mb * (a.Npad / 128), ngroups = a.K / a.group;
-    // Mid M (int4 g128): 32 x 128 tiles of 4 waves streaming the whole K -- no K split, hence no
-    // f32 slabs and no combine launch -- where they give a full round but 64 x 128 tiles do not
-    // (M 225..448 at N = 4096, where the policy below splits K): M 256 / 384: 25.1 -> 20.4 /
-    // 30.0 -> 24.6 us; at M >= 512 the 64 x 128 two-k-group tiles stay faster (23.1 vs 25.8 us)
-    // (profiles/r03_midm/policy_ab.json).
-    if constexpr (G64 == 2 && BITS == 4 && DLLM_EXACT_WREG) {
-        const int t32 = ((a.M + 31) / 32) * (a.Npad / 128), t64 = ((a.M + 63) / 64) * (a.Npad / 128);
-        if (a.lab_policy != 1 && tiles < kCUs && t64 < kCUs && t32 >= DLLM_MIDM_MINFILL) {
-#if DLLM_LAB
-            switch (a.lab_policy) {   // lab A/B: one k-group (RING 3) / two k-groups / four (RING 3)
-            case 2: return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, kMidRing>(a, 1, st);
-            case 3: if (ngroups % 2 == 0) return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
-                    break;
-            case 4: if (ngroups % 4 == 0) return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 3, 4>(a, 1, st);
-                    break;
-            default: break;
+    if constexpr (kI4G128) {
+        if (p.tile_m == 32) {
+            switch (p.kgroups) {
+            case 4: return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 2, 4>(a, 1, st);
+            case 2: return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
+            default: return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, kMidRing>(a, 1, st);
             }
-#endif
-            // k-groups of 4 waves sharing the tile (k-group g streams the g-th part of K; sums handed
-            // to k-group 0 through the ring): four (16 waves, one block per CU) while the grid is
-            // one block per CU, else two (8 waves, two blocks per CU fit).  M 256: 20.4 (one
-            // k-group) -> 15.5 (two) -> 14.3 us (four); M 384: 24.5 -> 22.1 (two) / 25.1 (four)
-            // (profiles/r03_midm/kgroups.jsonl).
-            if (t32 <= kCUs && ngroups % 4 == 0)
-                return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 2, 4>(a, 1, st);
-            if (ngroups % 2 == 0) return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
-            return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, kMidRing>(a, 1, st);
         }
-    }
 #if DLLM_EXACT_KG2
-    // tile-starved grids: 128 x 128 (or 64 x 128) tiles with two k-groups of 4 waves per block
-    if constexpr (G64 == 2 && BITS == 4 && DLLM_EXACT_WREG) {
-        // (lab A/B policy 5: 64 x 128 tiles, two blocks per CU, where 128 x 128 tiles give one round;
-        // 6 / 7: the 128 x 128 tiles with 64-deep stages in a 4- / 3-stage ring instead of 128-deep
-        // stages in a 2-stage ring)
-#if DLLM_LAB
-        if (tiles >= kCUs && tiles < 2 * kCUs && ngroups % 2 == 0 && a.lab_policy == 6)
-            return launch_exact_tile<BITS, YT, 4, 4, 1, 2, EPI, false, 1, 4, 2>(a, 1, st);
-        if (tiles >= kCUs && tiles < 2 * kCUs && ngroups % 2 == 0 && a.lab_policy == 7)
-            return launch_exact_tile<BITS, YT, 4, 4, 1, 2, EPI, false, 1, 3, 2>(a, 1, st);
+        if (p.kgroups == 2)
+            return p.tile_m == 128 ? launch_exact_tile<BITS, YT, 4, 4, 2, 1, EPI, false, 1, 2, 2>(a, 1, st)
+                                   : launch_exact_tile<BITS, YT, 4, 2, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
 #endif
-        if (tiles >= kCUs && tiles < 2 * kCUs && ngroups % 2 == 0 && a.lab_policy != 5)
-            return launch_exact_tile<BITS, YT, 4, 4, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
-        const int t64 = ((a.M + 63) / 64) * (a.Npad / 128);
-        if ((tiles < kCUs || a.lab_policy == 5) && t64 >= kCUs && ngroups % 2 == 0)
-            return launch_exact_tile<BITS, YT, 4, 2, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
     }
-#endif
+    if (p.kgroups != 1 || p.tile_n != 128) return fail(DLLM_ERR_UNSUPPORTED, "exact GEMM: no kernel for the plan");
 #if DLLM_EXACT_MR2
-    if (tiles < 2 * kCUs) {
-        const int t64 = ((a.M + 63) / 64) * (a.Npad / 128);
-        int ns = 1;
-        while (t64 * ns < 2 * kCUs && ns < 8 && ngroups % (2 * ns) == 0 && (a.K / kBK) / (2 * ns) >= 4) ns *= 2;
-        return launch_exact_tile<BITS, YT, 4, 2, 1, G64, EPI>(a, ns, st);
-    }
+    if (p.tile_m == 64) return launch_exact_tile<BITS, YT, 4, 2, 1, G64, EPI>(a, ns, st);
 #endif
-    int nsplit = 1;
-    while (tiles * nsplit < 200 && nsplit < 8 && ngroups % (2 * nsplit) == 0 && (a.K / kBK) / (2 * nsplit) >= 4)
-        nsplit *= 2;
-    return launch_exact_tile<BITS, YT, 4, 4, 1, G64, EPI>(a, nsplit, st);
+    return launch_exact_tile<BITS, YT, 4, 4, 1, G64, EPI>(a, ns, st);
 }
 
 template <int KPG, int EPI>
@@ -1172,6 +1233,10 @@ int launch_exact_kpg(const ExactGemmArgs &a, int y_f32, hipStream_t st) {
 #if DLLM_STAMP
 DLLM_STAMP_READER(dllm_stamp_read_exact, g_stamp_exact)
 #endif
+
+void select_exact_plan(int bits, int M, int K, int Npad, int group, dllm_linear_plan_t *p) {
+    exact_plan(bits, M, K, Npad, group, p);
+}
 
 bool exact_gemm_supported(int M, int K, int Npad, int group) {
     return M >= 1 && Npad % 128 == 0 && K % group == 0 && (group == 64 || group == 128 || group == 256);

@@ -1132,10 +1132,35 @@ inline size_t xl_lds_bytes(int M, int K, int group) {
     return static_cast<size_t>(M + 1) * (2 * static_cast<size_t>(K) + 16) + 2 * nq * 256;
 }
 
+// What the kernel selection reads of a layer: a handle's facts (plan_shape_of) or the arguments of
+// dllm_linear_plan_shape.  horner_ok = the create's check of the Horner ratios passed (hstate == 1).
+struct PlanShape {
+    size_t K = 0, N = 0, Npad = 0, group = 0;
+    int bits = 0, precision = DLLM_PRECISION_EXACT;
+    bool horner_ok = false, decode_layout = false;
+#if DLLM_LAB
+    int variant = -1;   // lab A/B: the handle's schedule variant
+#endif
+};
+inline PlanShape plan_shape_of(const dllm_linear *h) {
+    PlanShape s;
+    s.K = h->K; s.N = h->N; s.Npad = h->Npad; s.group = h->group;
+    s.bits = h->bits; s.precision = h->precision;
+    s.horner_ok = h->hstate == 1; s.decode_layout = h->wdec != nullptr;
+#if DLLM_LAB
+    s.variant = h->variant;
+#endif
+    return s;
+}
+
 // Exact-weight kernels apply when the group tiles K (a stage never straddles two groups).
-inline bool use_exact(const dllm_linear *h) {
+inline bool use_exact(const PlanShape *h) {
     return h->precision == DLLM_PRECISION_EXACT &&
            exact_gemm_supported(1, static_cast<int>(h->K), static_cast<int>(h->Npad), static_cast<int>(h->group));
+}
+inline bool use_exact(const dllm_linear *h) {
+    const PlanShape s = plan_shape_of(h);
+    return use_exact(&s);
 }
 
 // Decode tile policy: (NT, nsplit) per M bucket, chosen from the M-sweep.
@@ -1148,22 +1173,43 @@ inline void decode_policy(int M, int &nt, int &nsplit) {
     nt = nsplit = M > 32 ? 4 : 1;
 }
 
+// The decode plan for M <= kDecodeMaxM rows: tile_m = the M bucket (16 MT), tile_n = 16 NT, nsplit
+// K slices of whole 128-deep slabs, DLLM_PLAN_DECODE_XL where X is staged in LDS.  nt0 / nsplit0 > 0:
+// the lab build's (NT, nsplit) override in place of decode_policy.
+inline void decode_plan(const PlanShape *h, int M, dllm_linear_plan_t *p, int nt0 = 0, int nsplit0 = 0) {
+    int nt, nsplit;
+    decode_policy(M, nt, nsplit);
+    if (nt0 > 0) { nt = nt0; nsplit = nsplit0; }
+    // the column group must tile Npad (a multiple of 128)
+    while (nt > 1 && h->Npad % (16 * nt)) nt /= 2;
+    const int K = static_cast<int>(h->K), gr = static_cast<int>(h->group);
+    const int nslab = (K + 127) / 128;
+    nsplit = std::max(1, std::min(nsplit, nslab));
+    p->kernel = DLLM_KERNEL_DECODE;
+    p->tile_m = M <= 16 ? 16 : (M <= 32 ? 32 : 64);
+    p->tile_n = 16 * nt;
+    p->kgroups = 1;
+    p->nsplit = nsplit;
+    p->flags = nsplit > 1 ? DLLM_PLAN_SPLITK : 0;
+    // M 9..16 only: M = 16 6.75 vs 7.25 us per layer in the 40-layer chain, M = 1 / 2 / 4 / 8
+    // 5.16 / 5.34 / 5.58 / 6.00 vs 5.18 / 5.38 / 5.47 / 5.94 (profiles/r05_decode_xl/): fewer
+    // load instructions do not shorten the M <= 8 layer, whose time is the weight stream's
+    // latency, and the DMA wait + barrier before the first MFMA costs a little there.
+    if (DLLM_DECODE_XL && nsplit == 1 && nt == 1 && M <= 16 && use_exact(h) && gr != 64 && M > 8 && K % 512 == 0 &&
+        nslab >= kDecWaves && xl_lds_bytes(M, K, gr) <= kXlLdsMax)
+        p->flags |= DLLM_PLAN_DECODE_XL;
+}
+
 template <int BITS, typename YT, int MT, int NT, int EXACT>
-int launch_decode_nt(const dllm_linear *h, const __half *X, int M, YT *Y, int nsplit, hipStream_t st) {
+int launch_decode_nt(const dllm_linear *h, const __half *X, int M, YT *Y, int nsplit, bool xl, hipStream_t st) {
     const unsigned nbx = static_cast<unsigned>(h->Npad / (16 * NT));
     const int K = static_cast<int>(h->K), N = static_cast<int>(h->N);
     const int Np = static_cast<int>(h->Npad), gr = static_cast<int>(h->group);
-    const int nslab = (K + 127) / 128;
-    nsplit = std::max(1, std::min(nsplit, nslab));
     if (nsplit == 1) {
 #if DLLM_DECODE_XL
         if constexpr (MT == 1 && NT == 1 && EXACT == 2) {
-            const size_t bytes = xl_lds_bytes(M, K, gr);
-            // M 9..16 only: M = 16 6.75 vs 7.25 us per layer in the 40-layer chain, M = 1 / 2 / 4 / 8
-            // 5.16 / 5.34 / 5.58 / 6.00 vs 5.18 / 5.38 / 5.47 / 5.94 (profiles/r05_decode_xl/): fewer
-            // load instructions do not shorten the M <= 8 layer, whose time is the weight stream's
-            // latency, and the DMA wait + barrier before the first MFMA costs a little there.
-            if (M > 8 && K % 512 == 0 && nslab >= kDecWaves && bytes <= kXlLdsMax) {
+            if (xl) {   // DLLM_PLAN_DECODE_XL (decode_plan)
+                const size_t bytes = xl_lds_bytes(M, K, gr);
                 auto *kern = &wq_decode_kernel<BITS, YT, 1, 1, false, 0, 2, kDecWaves, true>;
                 // the dynamic-LDS limit, set once per device (a bit per device id; a process may drive
                 // several GPUs)
@@ -1211,20 +1257,23 @@ int launch_decode_nt(const dllm_linear *h, const __half *X, int M, YT *Y, int ns
 }
 
 template <int BITS, typename YT, int MT, int EXACT>
-int launch_decode_mt(const dllm_linear *h, const __half *X, int M, YT *Y, int nt, int nsplit, hipStream_t st) {
-    switch (nt) {
-    case 2: return launch_decode_nt<BITS, YT, MT, 2, EXACT>(h, X, M, Y, nsplit, st);
-    case 4: return launch_decode_nt<BITS, YT, MT, 4, EXACT>(h, X, M, Y, nsplit, st);
-    default: return launch_decode_nt<BITS, YT, MT, 1, EXACT>(h, X, M, Y, nsplit, st);
+int launch_decode_mt(const dllm_linear *h, const __half *X, int M, YT *Y, const dllm_linear_plan_t &p, hipStream_t st) {
+    const bool xl = (p.flags & DLLM_PLAN_DECODE_XL) != 0;
+    switch (p.tile_n / 16) {
+    case 2: return launch_decode_nt<BITS, YT, MT, 2, EXACT>(h, X, M, Y, p.nsplit, xl, st);
+    case 4: return launch_decode_nt<BITS, YT, MT, 4, EXACT>(h, X, M, Y, p.nsplit, xl, st);
+    default: return launch_decode_nt<BITS, YT, MT, 1, EXACT>(h, X, M, Y, p.nsplit, xl, st);
     }
 }
 
 template <int BITS, typename YT, int EXACT>
-int launch_decode_x(const dllm_linear *h, const __half *X, size_t M, YT *Y, int nt, int nsplit, hipStream_t st) {
+int launch_decode_x(const dllm_linear *h, const __half *X, size_t M, YT *Y, const dllm_linear_plan_t &p, hipStream_t st) {
     const int Mi = static_cast<int>(M);
-    if (M <= 16) return launch_decode_mt<BITS, YT, 1, EXACT>(h, X, Mi, Y, nt, nsplit, st);
-    if (M <= 32) return launch_decode_mt<BITS, YT, 2, EXACT>(h, X, Mi, Y, nt, nsplit, st);
-    return launch_decode_mt<BITS, YT, 4, EXACT>(h, X, Mi, Y, nt, nsplit, st);
+    switch (p.tile_m) {
+    case 16: return launch_decode_mt<BITS, YT, 1, EXACT>(h, X, Mi, Y, p, st);
+    case 32: return launch_decode_mt<BITS, YT, 2, EXACT>(h, X, Mi, Y, p, st);
+    default: return launch_decode_mt<BITS, YT, 4, EXACT>(h, X, Mi, Y, p, st);
+    }
 }
 
 #if DLLM_LAB
@@ -1251,24 +1300,20 @@ int ensure_decode_layout(const dllm_linear *h, hipStream_t) {
 }
 
 template <int BITS, typename YT>
-int launch_decode(const dllm_linear *h, const __half *X, size_t M, YT *Y, hipStream_t st) {
+int launch_decode(const dllm_linear *h, const __half *X, size_t M, YT *Y, dllm_linear_plan_t p, hipStream_t st) {
     if (const int rc = ensure_decode_layout(h, st)) return rc;
-    int nt, nsplit;
-    decode_policy(static_cast<int>(M), nt, nsplit);
 #if DLLM_LAB
     if (M <= 16 && h->dlab != 0) return launch_decode_lab<BITS, YT>(h, X, M, Y, st);
     if (h->dcfg > 0) {   // dcfg = 16 log2(NT) + log2(nsplit) + 1
-        nt = 1 << ((h->dcfg - 1) / 16);
-        nsplit = 1 << ((h->dcfg - 1) % 16);
+        const PlanShape s = plan_shape_of(h);
+        decode_plan(&s, static_cast<int>(M), &p, 1 << ((h->dcfg - 1) / 16), 1 << ((h->dcfg - 1) % 16));
     }
 #endif
-    // the column group must tile Npad (a multiple of 128)
-    while (nt > 1 && h->Npad % (16 * nt)) nt /= 2;
     if (use_exact(h)) {
-        if (h->group == 64) return launch_decode_x<BITS, YT, 1>(h, X, M, Y, nt, nsplit, st);
-        return launch_decode_x<BITS, YT, 2>(h, X, M, Y, nt, nsplit, st);
+        if (h->group == 64) return launch_decode_x<BITS, YT, 1>(h, X, M, Y, p, st);
+        return launch_decode_x<BITS, YT, 2>(h, X, M, Y, p, st);
     }
-    return launch_decode_x<BITS, YT, 0>(h, X, M, Y, nt, nsplit, st);
+    return launch_decode_x<BITS, YT, 0>(h, X, M, Y, p, st);
 }
 
 // 3-stage-ring GEMM (rounded weights) with tile (32 MR) x (32 NW), K optionally split into nsplit slices.
@@ -1322,18 +1367,29 @@ int launch_ring(const dllm_linear *h, const __half *X, int M, YT *Y, hipStream_t
 // Rounded-weight (DLLM_PRECISION_F16W) tile policy: the largest tile that still gives >= 256
 // blocks -- 256 x 256 (8 waves), 256 x 128 (8 waves, two k-groups) -- below that 128 x 128 tiles
 // (two k-groups) with K split until ~200+ blocks (slab partials + ordered combine).
-template <int BITS, typename YT, int EPI = 0>
-int launch_rounded(const dllm_linear *h, const __half *X, int M, YT *Y, hipStream_t st,
-                   const PSampleEpi *epi = nullptr) {
+inline void rounded_plan(const PlanShape *h, int M, dllm_linear_plan_t *p) {
     const int np = static_cast<int>(h->Npad);
     const int mb256 = (M + 255) / 256, mb128 = (M + 127) / 128;
-    if (np % 256 == 0 && mb256 * (np / 256) >= kCUs) return launch_ring<BITS, YT, 8, 8, 1, EPI>(h, X, M, Y, st, 1, epi);
-    if (mb256 * (np / 128) >= kCUs) return launch_ring<BITS, YT, 4, 8, 2, EPI>(h, X, M, Y, st, 1, epi);
+    auto set = [&](int tm, int tn, int kg, int ns) {
+        p->kernel = DLLM_KERNEL_ROUNDED_RING;
+        p->tile_m = tm; p->tile_n = tn; p->kgroups = kg; p->nsplit = ns;
+        p->flags = ns > 1 ? DLLM_PLAN_SPLITK : 0;
+    };
+    if (np % 256 == 0 && mb256 * (np / 256) >= kCUs) return set(256, 256, 1, 1);
+    if (mb256 * (np / 128) >= kCUs) return set(256, 128, 2, 1);
     const int tiles = mb128 * (np / 128);
     const int nk = static_cast<int>(h->K / kBK);
     int nsplit = 1;
     while (tiles * nsplit < 200 && nsplit < 8 && nk % (2 * nsplit) == 0 && nk / (2 * nsplit) >= 4) nsplit *= 2;
-    return launch_ring<BITS, YT, 4, 4, 2, EPI>(h, X, M, Y, st, nsplit, epi);
+    return set(128, 128, 2, nsplit);
+}
+
+template <int BITS, typename YT, int EPI = 0>
+int launch_rounded(const dllm_linear *h, const __half *X, int M, YT *Y, hipStream_t st, const dllm_linear_plan_t &p,
+                   const PSampleEpi *epi = nullptr) {
+    if (p.tile_n == 256) return launch_ring<BITS, YT, 8, 8, 1, EPI>(h, X, M, Y, st, 1, epi);
+    if (p.tile_m == 256) return launch_ring<BITS, YT, 4, 8, 2, EPI>(h, X, M, Y, st, 1, epi);
+    return launch_ring<BITS, YT, 4, 4, 2, EPI>(h, X, M, Y, st, p.nsplit, epi);
 }
 
 // Exact-weight GEMM in Horner form (wq_gemm8_kernel<..., HORNER>, 256 x 256 tiles): for int4 g128
@@ -1347,13 +1403,13 @@ inline bool lab_horner128() {
 #endif
 
 // int4 and (256 x 256 tiles only: horner_ready) int2 codes, group 128.
-inline bool horner_shape(const dllm_linear *h) {
+inline bool horner_shape(const PlanShape *h) {
     return h->precision == DLLM_PRECISION_EXACT && (h->bits == 4 || h->bits == 2) && h->group == 128 &&
            h->K % 128 == 0 && h->Npad % 256 == 0;
 }
 
 // The handle's Horner ratios are valid (decided at create, immutable afterwards).
-inline bool ensure_horner(const dllm_linear *h, hipStream_t) { return h->hstate == 1; }
+inline bool ensure_horner(const PlanShape *h) { return h->horner_ok; }
 
 // DLLM_POLICY_ROUNDS (product; 0 = the earlier full-round thresholds, A/B): a grid short of a round
 // takes the larger tiles when the alternative needs more rounds -- a 256 x 256 Horner round takes
@@ -1365,7 +1421,7 @@ inline bool ensure_horner(const dllm_linear *h, hipStream_t) { return h->hstate 
 #ifndef DLLM_POLICY_ROUNDS
 #define DLLM_POLICY_ROUNDS 1
 #endif
-bool horner_ready(const dllm_linear *hc, int M, hipStream_t st) {
+bool horner_ready(const PlanShape *hc, int M) {
     const int np = static_cast<int>(hc->Npad);
     if (!horner_shape(hc)) return false;
     // rounds of 256 tiles: a 256 x 256 round takes about two 128 x 256 rounds, so the Horner grid
@@ -1379,7 +1435,7 @@ bool horner_ready(const dllm_linear *hc, int M, hipStream_t st) {
 #endif
     if ((!DLLM_POLICY_ROUNDS && t256 < kCUs) || 2 * ((t256 + kCUs - 1) / kCUs) > (t128 + kCUs - 1) / kCUs)
         return false;
-    return ensure_horner(hc, st);
+    return ensure_horner(hc);
 }
 
 // The Horner kernel on 128-token tiles (wq_horner16_kernel<..., TB = 8>, x 256 columns, 128-deep
@@ -1389,9 +1445,9 @@ bool horner_ready(const dllm_linear *hc, int M, hipStream_t st) {
 // 64.9 vs 66.7 us, 72.5 vs 67.0 us; profiles/r04_horner/), so the fold form stays the product path.
 // Returns the tile rows, 0 = not applicable.
 #if DLLM_LAB
-int horner_rows(const dllm_linear *hc, int M) {
+int horner_rows(const PlanShape *hc, int M) {
     const int np = static_cast<int>(hc->Npad);
-    if (hc->variant != 323 || hc->bits != 4 || !horner_shape(hc) || hc->hstate != 1) return 0;
+    if (hc->variant != 323 || hc->bits != 4 || !horner_shape(hc) || !hc->horner_ok) return 0;
     if (((M + 127) / 128) * (np / 256) >= kCUs) return 128;
     return 0;
 }
@@ -1401,11 +1457,14 @@ int horner_rows(const dllm_linear *hc, int M) {
 // nor the fold form's 128 x 256 grid fills a round but the 256 x 128 grid does (N = 4096: M
 // 1793..1920; measured at M = 1800: 69.2 vs 74.9 us).  At M = 2048 the 128 x 256 fold grid fills
 // the chip and is as fast (68.5 vs 69.6 us: KG2 stages two K-halves' X slices, 72 KiB per k-step
-// against 24 KiB for the same MFMAs; profiles/r03_kg2/).
-bool horner_kg2_ready(const dllm_linear *hc, int M) {
+// against 24 KiB for the same MFMAs; profiles/r03_kg2/).  prefill_plan asks horner_pc_ready first,
+// which since DLLM_POLICY_ROUNDS takes M 1793..1920 at N = 4096 (240 PC tiles against two rounds of
+// 128 x 128): what reaches this kernel now is ceil(M / 128) == ceil(M / 256), i.e. M <= 128, on 256
+// to 510 column tiles of 128 (M = 100, K = 512, N = 32768; tests/test_gpu_linear_kernels.py).
+bool horner_kg2_ready(const PlanShape *hc, int M) {
     const int np = static_cast<int>(hc->Npad);
     if (!(hc->precision == DLLM_PRECISION_EXACT && hc->bits == 4 && hc->group == 128 && hc->K % 256 == 0 &&
-          np % 128 == 0 && hc->hstate == 1))
+          np % 128 == 0 && hc->horner_ok))
         return false;
 #if DLLM_LAB
     if (hc->variant == 14 || hc->variant == 28) return false;   // lab A/B: the fold-form exact policy
@@ -1421,21 +1480,21 @@ bool horner_kg2_ready(const dllm_linear *hc, int M) {
 #ifndef DLLM_HORNER_PC
 #define DLLM_HORNER_PC 1
 #endif
-bool horner_pc_ready(const dllm_linear *hc, int M, hipStream_t st) {
+bool horner_pc_ready(const PlanShape *hc, int M) {
 #if DLLM_HORNER_PC
     const int np = static_cast<int>(hc->Npad);
-    if (hc->bits != 4 || !horner_shape(hc) || hc->hstate != 1) return false;
+    if (hc->bits != 4 || !horner_shape(hc) || !hc->horner_ok) return false;
 #if DLLM_LAB
     if (hc->variant == 14 || hc->variant == 28) return false;   // lab A/B: the fold-form exact policy
 #endif
     const int t128 = ((M + 127) / 128) * (np / 256);
-    if (horner_ready(hc, M, st)) return false;
+    if (horner_ready(hc, M)) return false;
     if (t128 >= kCUs) return true;
     if (!DLLM_POLICY_ROUNDS || np % 128 != 0 || hc->K % 256 != 0) return false;
     const int tk = ((M + 127) / 128) * (np / 128);   // the two-k-group 128 x 128 grid
     return 178 * ((t128 + kCUs - 1) / kCUs) <= 100 * ((tk + kCUs - 1) / kCUs);
 #else
-    (void)hc; (void)M; (void)st;
+    (void)hc; (void)M;
     return false;
 #endif
 }
@@ -1459,17 +1518,16 @@ bool horner_pc_ready(const dllm_linear *hc, int M, hipStream_t st) {
 #ifndef DLLM_PC_KG2_SMALL   // 64- and 32-token tiles too
 #define DLLM_PC_KG2_SMALL 0
 #endif
-bool horner_kg2_ready(const dllm_linear *hc, int M);
-int horner_pc_kg2_rows(const dllm_linear *hc, int M, hipStream_t st) {
+int horner_pc_kg2_rows(const PlanShape *hc, int M) {
 #if DLLM_HORNER_PC_KG2
     const int np = static_cast<int>(hc->Npad);
     if (!(hc->precision == DLLM_PRECISION_EXACT && hc->bits == 4 && hc->group == 128 && hc->K % 256 == 0 &&
-          np % 128 == 0 && hc->hstate == 1))
+          np % 128 == 0 && hc->horner_ok))
         return 0;
 #if DLLM_LAB
     if (hc->variant == 14 || hc->variant == 28) return 0;   // lab A/B: the fold-form exact policy
 #endif
-    if (horner_ready(hc, M, st) || horner_pc_ready(hc, M, st) || horner_kg2_ready(hc, M)) return 0;
+    if (horner_ready(hc, M) || horner_pc_ready(hc, M) || horner_kg2_ready(hc, M)) return 0;
 #if DLLM_PC_KG2_SMALL
     for (int rows = 128; rows >= 32; rows /= 2) {
         const int t = ((M + rows - 1) / rows) * (np / 128);
@@ -1490,7 +1548,7 @@ int horner_pc_kg2_rows(const dllm_linear *hc, int M, hipStream_t st) {
     return t64 >= DLLM_PC_KG2_MINFILL ? 64 : 0;
 #endif
 #else
-    (void)hc; (void)M; (void)st;
+    (void)hc; (void)M;
     return 0;
 #endif
 }
@@ -1540,14 +1598,45 @@ inline ExactGemmArgs exact_args(const dllm_linear *h, const __half *X, int M, vo
     return a;
 }
 
-// Prefill (M > kDecodeMaxM) dispatch: exact-weight kernels (default precision) or the rounded ring.
+// The one kernel selection of the linear layer: dllm_linear_plan(_shape) report it and the launchers
+// below switch on it.  Prefill (M > kDecodeMaxM, or no decode layout): the exact-weight kernels
+// (default precision) -- the Horner family where its grids fit, else the fold-form tiles
+// (select_exact_plan) -- or the rounded ring.
+inline void prefill_plan(const PlanShape *h, int M, dllm_linear_plan_t *p) {
+    if (!use_exact(h)) return rounded_plan(h, M, p);
+    auto horner = [&](int kernel, int tm, int tn, int kg) {
+        p->kernel = kernel;
+        p->tile_m = tm; p->tile_n = tn; p->kgroups = kg; p->nsplit = 1;
+        p->flags = 0;
+    };
+    if ((h->bits == 4 || h->bits == 2) && horner_ready(h, M)) return horner(DLLM_KERNEL_HORNER16, 256, 256, 1);
+    if (h->bits == 4 && horner_pc_ready(h, M)) return horner(DLLM_KERNEL_HORNER_PC, 128, 256, 1);
+    if (h->bits == 4 && horner_kg2_ready(h, M)) return horner(DLLM_KERNEL_HORNER_KG2, 256, 128, 2);
+    if (const int rows = h->bits == 4 ? horner_pc_kg2_rows(h, M) : 0)
+        return horner(DLLM_KERNEL_HORNER_PC_KG2, rows, 128, 2);
+    select_exact_plan(h->bits, M, static_cast<int>(h->K), static_cast<int>(h->Npad), static_cast<int>(h->group), p);
+}
+
+// `fused`: the plan of dllm_linear_forward_psample(_ex), whose M <= kDecodeMaxM calls run the plain
+// GEMM and the p_sample kernel.
+inline void select_plan(const PlanShape *h, size_t M, int fused, dllm_linear_plan_t *p) {
+    if (M <= static_cast<size_t>(kDecodeMaxM) && h->decode_layout) decode_plan(h, static_cast<int>(M), p);
+    else prefill_plan(h, static_cast<int>(M), p);
+    if (fused && M <= static_cast<size_t>(kDecodeMaxM)) p->flags |= DLLM_PLAN_NOT_FUSED;
+}
+
 template <int BITS, typename YT, int EPI = 0>
 int launch_prefill_auto(const dllm_linear *h, const __half *X, int M, YT *Y, hipStream_t st,
-                        const PSampleEpi *epi = nullptr) {
+                        const dllm_linear_plan_t &p, const PSampleEpi *epi = nullptr) {
 #if DLLM_LAB
     // lab A/B: 4 = the rounded policy, 14 / 15 = exact (128 x 256 / tile-major 256 x 256), others
-    // = the round-1 schedules; -1 (default) = the product policy below
-    if (h->variant == 4) return launch_rounded<BITS, YT, EPI>(h, X, M, Y, st, epi);
+    // = the round-1 schedules; -1 (default) = the product plan
+    if (h->variant == 4) {
+        const PlanShape s = plan_shape_of(h);
+        dllm_linear_plan_t rp;
+        rounded_plan(&s, M, &rp);
+        return launch_rounded<BITS, YT, EPI>(h, X, M, Y, st, rp, epi);
+    }
     if ((h->variant == 14 || h->variant == 15) && exact_gemm_supported(M, (int)h->K, (int)h->Npad, (int)h->group))
         return launch_exact_gemm(exact_args(h, X, M, Y, epi), std::is_same<YT, float>::value ? 1 : 0, st);
     if (h->variant >= 0) {
@@ -1555,48 +1644,56 @@ int launch_prefill_auto(const dllm_linear *h, const __half *X, int M, YT *Y, hip
         if (rc >= 0) return rc;
     }
 #endif
-    if (use_exact(h)) {
-        if ((BITS == 4 || BITS == 2) && horner_ready(h, M, st)) return launch_horner<YT, EPI>(h, X, M, Y, st, epi);
-        if (BITS == 4 && horner_pc_ready(h, M, st)) {
-            const HornerGemmArgs a{X, M, (int)h->K, h->wdev, h->sz, h->hr, h->sf, h->bias, Y, (int)h->N,
-                                   (int)h->Npad, epi};
-            return launch_horner_pc_gemm(a, std::is_same<YT, float>::value ? 1 : 0, st);
-        }
-        if (BITS == 4 && horner_kg2_ready(h, M)) {
-            const HornerGemmArgs a{X, M, (int)h->K, h->wdev, h->sz, h->hr, h->sf, h->bias, Y, (int)h->N,
-                                   (int)h->Npad, epi};
-            return launch_horner_kg2_gemm(a, std::is_same<YT, float>::value ? 1 : 0, st);
-        }
-        if (const int rows = BITS == 4 ? horner_pc_kg2_rows(h, M, st) : 0) {
-            const HornerGemmArgs a{X, M, (int)h->K, h->wdev, h->sz, h->hr, h->sf, h->bias, Y, (int)h->N,
-                                   (int)h->Npad, epi};
-            return launch_horner_pc_kg2_gemm(a, rows, std::is_same<YT, float>::value ? 1 : 0, st);
-        }
+    const int y_f32 = std::is_same<YT, float>::value ? 1 : 0;
+    const HornerGemmArgs ha{X, M, (int)h->K, h->wdev, h->sz, h->hr, h->sf, h->bias, Y, (int)h->N, (int)h->Npad, epi};
+    switch (p.kernel) {
+    case DLLM_KERNEL_HORNER16:
+        if constexpr (BITS == 4 || BITS == 2) return launch_horner<YT, EPI>(h, X, M, Y, st, epi);
+        break;
+    case DLLM_KERNEL_HORNER_PC:
+        if constexpr (BITS == 4) return launch_horner_pc_gemm(ha, y_f32, st);
+        break;
+    case DLLM_KERNEL_HORNER_KG2:
+        if constexpr (BITS == 4) return launch_horner_kg2_gemm(ha, y_f32, st);
+        break;
+    case DLLM_KERNEL_HORNER_PC_KG2:
+        if constexpr (BITS == 4) return launch_horner_pc_kg2_gemm(ha, p.tile_m, y_f32, st);
+        break;
+    case DLLM_KERNEL_EXACT_FOLD: {
 #if DLLM_LAB
-        if (const int rows = BITS == 4 ? horner_rows(h, M) : 0) {   // lab A/B 323 only
-            const HornerGemmArgs a{X, M, (int)h->K, h->wdev, h->sz, h->hr, h->sf, h->bias, Y, (int)h->N,
-                                   (int)h->Npad, epi};
-            return launch_horner_rows_gemm(a, rows, std::is_same<YT, float>::value ? 1 : 0, st);
-        }
+        const PlanShape s = plan_shape_of(h);
+        if (const int rows = BITS == 4 ? horner_rows(&s, M) : 0)   // lab A/B 323 only
+            return launch_horner_rows_gemm(ha, rows, y_f32, st);
 #endif
         ExactGemmArgs a = exact_args(h, X, M, Y, epi);
 #if DLLM_EXACT_HORNER   // A/B build: the 128 x 256 exact tiles in Horner form too
-        if (BITS == 4 && ensure_horner(h, st)) a.hr = h->hr;
+        if (BITS == 4 && h->hstate == 1) a.hr = h->hr;
 #endif
-        return launch_exact_gemm(a, std::is_same<YT, float>::value ? 1 : 0, st);
+        return launch_exact_gemm(a, y_f32, st);
     }
-    return launch_rounded<BITS, YT, EPI>(h, X, M, Y, st, epi);
+    case DLLM_KERNEL_ROUNDED_RING: return launch_rounded<BITS, YT, EPI>(h, X, M, Y, st, p, epi);
+    default: break;
+    }
+    return fail(DLLM_ERR_UNSUPPORTED, "linear forward: no kernel for the plan");
 }
 
 template <int BITS, typename YT>
 int launch_gemm_t(const dllm_linear *h, const __half *X, size_t M, YT *Y, hipStream_t st) {
-    if (M <= static_cast<size_t>(kDecodeMaxM) && h->wdec) return launch_decode<BITS, YT>(h, X, M, Y, st);
-    return launch_prefill_auto<BITS, YT>(h, X, static_cast<int>(M), Y, st);
+    const PlanShape s = plan_shape_of(h);
+    dllm_linear_plan_t p;
+    select_plan(&s, M, 0, &p);
+    if (p.kernel == DLLM_KERNEL_DECODE) return launch_decode<BITS, YT>(h, X, M, Y, p, st);
+    return launch_prefill_auto<BITS, YT>(h, X, static_cast<int>(M), Y, st, p);
 }
 
 template <int BITS>
 int psample_fused(dllm_linear *h, const __half *Xh, int M, const PSampleEpi &ep, hipStream_t st) {
-    return launch_prefill_auto<BITS, float, 1>(h, Xh, M, ep.x_prev, st, &ep);
+    const PlanShape s = plan_shape_of(h);
+    dllm_linear_plan_t p;
+    select_plan(&s, static_cast<size_t>(M), 1, &p);
+    if (p.kernel == DLLM_KERNEL_DECODE || (p.flags & DLLM_PLAN_NOT_FUSED))
+        return fail(DLLM_ERR_UNSUPPORTED, "fused p_sample: the plan has no fused epilogue");
+    return launch_prefill_auto<BITS, float, 1>(h, Xh, M, ep.x_prev, st, p, &ep);
 }
 
 template <int BITS>
@@ -1683,7 +1780,8 @@ int finish_linear(dllm_linear *h, const uint32_t *canon, const float *scales, co
     build_sf_kernel<<<gs, 256, 0, st>>>(scales, h->G, h->N, h->Npad, h->sf);
     DLLM_LAUNCH_CHECK();
     int *flag = nullptr, unsafe = 1;
-    if (horner_shape(h)) {
+    const PlanShape shape = plan_shape_of(h);
+    if (horner_shape(&shape)) {
         DLLM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->hr), (h->G + 1) * h->Npad * 4));
         DLLM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&flag), sizeof(int)));
         hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st);
@@ -1876,7 +1974,12 @@ int dllm_linear_forward_psample_ex(dllm_linear_t h, const void *X, size_t M, int
     hipStream_t st = as_stream(stream);
     const __half *Xh = nullptr;
     if (const int rc = prepare_x(h, X, M, x_dtype, st, &Xh)) return rc;
-    bool fused = M > static_cast<size_t>(kDecodeMaxM);
+    dllm_linear_plan_t plan;
+    {
+        const PlanShape shape = plan_shape_of(h);
+        select_plan(&shape, M, 1, &plan);
+    }
+    bool fused = !(plan.flags & DLLM_PLAN_NOT_FUSED);
 #if DLLM_LAB
     fused = fused && !((h->variant >= 0 && h->variant <= 3) || h->variant == 5 || h->variant == 6);
 #endif
@@ -1943,6 +2046,31 @@ int dllm_linear_info(dllm_linear_t h, size_t *K, size_t *N, uint8_t *bits, size_
     if (N) *N = h->N;
     if (bits) *bits = static_cast<uint8_t>(h->bits);
     if (group) *group = h->group;
+    return DLLM_OK;
+}
+
+int dllm_linear_plan(dllm_linear_t h, size_t M, int fused, dllm_linear_plan_t *out) {
+    if (!h || !out) return fail(DLLM_ERR_INVALID_PARAMS, "null argument");
+    if (M == 0 || M > (1u << 30)) return fail(DLLM_ERR_SHAPE_MISMATCH, "M must be 1..2^30");
+    if (fused && h->N % 4) return fail(DLLM_ERR_UNSUPPORTED, "fused p_sample needs N % 4 == 0");
+    const PlanShape s = plan_shape_of(h);
+    select_plan(&s, M, fused, out);
+    return DLLM_OK;
+}
+
+int dllm_linear_plan_shape(size_t K, size_t N, uint8_t bits, size_t group, int flags, int horner_ok, size_t M,
+                           int fused, dllm_linear_plan_t *out) {
+    if (!out) return fail(DLLM_ERR_INVALID_PARAMS, "null argument");
+    if (const int rc = check_shape(K, N, bits, group, flags)) return rc;
+    if (M == 0 || M > (1u << 30)) return fail(DLLM_ERR_SHAPE_MISMATCH, "M must be 1..2^30");
+    if (fused && N % 4) return fail(DLLM_ERR_UNSUPPORTED, "fused p_sample needs N % 4 == 0");
+    PlanShape s;
+    s.K = K; s.N = N; s.Npad = (N + kBN - 1) / kBN * kBN; s.group = group;
+    s.bits = bits; s.precision = flags & ~DLLM_LINEAR_PREFILL_ONLY;
+    s.decode_layout = (flags & DLLM_LINEAR_PREFILL_ONLY) == 0;
+    // a handle's ratios exist (and can pass the check) only for the Horner-form shapes
+    s.horner_ok = horner_ok != 0 && horner_shape(&s);
+    select_plan(&s, M, fused, out);
     return DLLM_OK;
 }
 

@@ -118,6 +118,13 @@ class QuantLinear:
         check(_lib.load().dllm_linear_export(self._h, _ptr(codes), _ptr(scales), _ptr(zps), _stream()))
         return codes, scales, zps
 
+    def plan(self, M: int, fused: bool = False) -> "_lib.LinearPlan":
+        """The kernel, tile and K split an M-row ``forward`` (``fused``: ``forward_psample``) launches
+        (dllm_linear_plan): the dispatch's own selection, answered on the host."""
+        plan = _lib.LinearPlan()
+        check(_lib.load().dllm_linear_plan(self._h, int(M), int(bool(fused)), C.byref(plan)))
+        return plan
+
     def device_bytes(self) -> int:
         """Device memory the handle owns (dllm_linear_device_bytes)."""
         return int(_lib.load().dllm_linear_device_bytes(self._h))

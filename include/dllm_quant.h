@@ -279,6 +279,41 @@ size_t dllm_linear_weight_bytes(dllm_linear_t h);
  * parameters (f16 zero-point/scale pairs + f32 scales) -- 17.02 MiB at 4096 x 4096 int4 g128, 9.02
  * MiB prefill-only -- plus the Horner ratios where kept (+0.52 MiB there). */
 size_t dllm_linear_device_bytes(dllm_linear_t h);
+
+/* Which kernel a forward of M rows launches, and on what tiles: the selection routine the dispatch
+ * itself switches on, so the answer cannot drift from what runs.  Host arithmetic only: no device
+ * call, no environment variable, no synchronisation.
+ *   kernel   DLLM_KERNEL_*;
+ *   tile_m, tile_n   rows x columns of one block's output tile (DECODE: the M bucket 16 / 32 / 64 and
+ *            16 columns per tile of the column group);
+ *   kgroups  wave groups of one block that share its tile: each streams its own part of K
+ *            (ROUNDED_RING: its own substeps of every 64-deep stage);
+ *   nsplit   K slices computed by separate blocks into f32 slabs (> 1: DLLM_PLAN_SPLITK is set);
+ *   flags    DLLM_PLAN_*.
+ * `fused` != 0 asks about dllm_linear_forward_psample(_ex): at M <= 64 it runs the plain GEMM and
+ * the p_sample kernel (DLLM_PLAN_NOT_FUSED), above that the same kernel with the fused epilogue. */
+enum dllm_linear_kernel {
+    DLLM_KERNEL_DECODE = 1,        /* the M <= 64 kernel on the decode layout */
+    DLLM_KERNEL_HORNER16 = 2,      /* Horner form, 256 x 256 tiles */
+    DLLM_KERNEL_HORNER_PC = 3,     /* Horner form, producer / consumer waves, 128 x 256 tiles */
+    DLLM_KERNEL_HORNER_KG2 = 4,    /* Horner form, 256 x 128 tiles, two k-groups */
+    DLLM_KERNEL_HORNER_PC_KG2 = 5, /* producer / consumer, 128 or 64 x 128 tiles, two k-groups */
+    DLLM_KERNEL_EXACT_FOLD = 6,    /* exact weights, the scale folded once per group */
+    DLLM_KERNEL_ROUNDED_RING = 7   /* f16-rounded weights (F16W, or EXACT where K % group != 0) */
+};
+enum dllm_linear_plan_flags {
+    DLLM_PLAN_STAGGERED = 1,  /* EXACT_FOLD 128 x 256: the two wave halves run half a step apart */
+    DLLM_PLAN_DECODE_XL = 2,  /* DECODE: X staged in LDS (M 9..16) */
+    DLLM_PLAN_SPLITK = 4,     /* a split-K combine launch follows the GEMM */
+    DLLM_PLAN_NOT_FUSED = 8   /* fused entry point at M <= 64: GEMM + p_sample kernel */
+};
+typedef struct { int32_t kernel, tile_m, tile_n, kgroups, nsplit, flags; } dllm_linear_plan_t;
+int dllm_linear_plan(dllm_linear_t h, size_t M, int fused, dllm_linear_plan_t *out);
+/* The same for a shape without a handle: `flags` as for the *_create_ex calls (precision |
+ * DLLM_LINEAR_PREFILL_ONLY), `horner_ok` = whether the create's check of the Horner ratios would
+ * pass for the scales (it only matters for int2 / int4 g128 EXACT shapes with Npad % 256 == 0). */
+int dllm_linear_plan_shape(size_t K, size_t N, uint8_t bits, size_t group, int flags, int horner_ok, size_t M,
+                           int fused, dllm_linear_plan_t *out);
 int dllm_linear_destroy(dllm_linear_t h);
 
 /* ---- f3: wire formats (host buffers; no device work) --------------------------------------

@@ -77,8 +77,16 @@ def test_add_noise_bit_exact(dllm, cuda, orc, cumprod):
     assert same(n2.cpu().numpy(), orc.add_noise(x0, ref_nz, coef))
 
 
-# (M, K, N, rows_per_sample): decode path (unfused), split-K (fused in the combine), 128-row ring,
-# 256x128 ring, 256x256 ring -- all with the fused entry point vs forward(f32) + p_sample.
+# (M, K, N, rows_per_sample), exact / rounded weights: decode path (unfused, both), the fold form's
+# 32 x 128 four-k-group tiles / the 128 x 128 ring with split-K (fused in the combine), the
+# two-k-group producer/consumer 128 x 128 tiles / the 128 x 128 ring (M 1024 and 4096 x N 1024), the
+# producer/consumer 128 x 256 tiles / the 256 x 128 ring, the 256 x 256 Horner tiles / 256 x 256 ring
+# -- all with the fused entry point vs forward(f32) + p_sample.  (Every fused epilogue at ragged
+# shapes and the other widths, against the oracle: tests/test_gpu_linear_kernels.py.)
+PSAMPLE_KERNELS = {48: ("DECODE", "DECODE"), 256: ("EXACT_FOLD", "ROUNDED_RING"), 1024: ("HORNER_PC_KG2", "ROUNDED_RING"),
+                   2048: ("HORNER_PC", "ROUNDED_RING"), 4096: ("HORNER16", "ROUNDED_RING")}
+
+
 @pytest.mark.parametrize("M,K,N,rps", [(48, 512, 256, 16), (256, 1024, 4096, 64), (1024, 256, 4096, 1024),
                                        (2048, 256, 4096, 512), (4096, 256, 4096, 4096), (4096, 512, 1024, 2048)])
 @pytest.mark.parametrize("precision", [0, 1])
@@ -88,6 +96,9 @@ def test_linear_psample_fused_bit_identical(dllm, cuda, M, K, N, rps, precision)
     W = 0.05 * torch.randn(K, N, device="cuda", generator=g)
     b = 0.1 * torch.randn(N, device="cuda", generator=g)
     lin = dllm.QuantLinear.from_weight(W, b, 4, 128, precision)
+    want = PSAMPLE_KERNELS[M][precision] if N == 4096 or M == 48 else ("HORNER_PC_KG2", "ROUNDED_RING")[precision]
+    plan = lin.plan(M, fused=True)
+    assert plan.astuple()[0] == want and bool(plan.flags & dllm._lib.PLAN_NOT_FUSED) == (M <= 64), plan
     X = torch.randn(M, K, device="cuda", generator=g).half()
     xt = torch.randn(M, N, device="cuda", generator=g)
     S = M // rps

@@ -454,10 +454,12 @@ def test_linear_policy_exact_integers(dllm, torch, orc, precision, bits, M, N):
     """Every tile of both precision policies on exact-integer data (each group spans [0, 2^b - 1]:
     scale 1, zp 0; K = 768 = 6 groups, so every product and partial sum is an exact integer):
     exact weights -- the Horner kernel (int4, M 4096 at N 4096), the producer/consumer 128 x 256
-    tiles (int4, M 2048; other widths: the 128 x 256 fold-form tiles), the KG2 Horner tiles (int4,
-    M 1800), the two-k-group producer/consumer 128 x 128 tiles (int4, N 1024 at M 4096),
-    128 x 128 + group-aligned split-K
-    (N 1024 / 512, M 512, 300), the exact decode kernel (M <= 64, one or 4 column tiles, K split) --
+    tiles (int4, M 2048, and M 1800 where their grid is short of a round; other widths: the
+    128 x 256 fold-form tiles at M 2048, 64 x 128 at M 1800), the two-k-group producer/consumer
+    128 x 128 and 64 x 128 tiles (int4, N 1024 and N 512 at M 4096), the fold form's 32 x 128
+    two-k-group tiles (int4, M 512 x N 1024, M 128 / 200) and 64 x 128 tiles with and without
+    group-aligned split-K (other widths; M 300), the exact decode kernel (M <= 64, one or 4 column
+    tiles, K split) --
     and rounded weights (256 x 256, 256 x 128 two k-groups, 128 x 128 split-K, decode), with bias,
     ragged M and a padded last column group: bit-equal to the f64 product, f32 and f16 outputs.
     N = 4092 (N % 8 == 4: every other output row starts 8-B aligned) takes the Horner grid (M 4096)
@@ -472,6 +474,17 @@ def test_linear_policy_exact_integers(dllm, torch, orc, precision, bits, M, N):
     b = rng.integers(-4, 5, N).astype(np.float32)
     lin = dllm.QuantLinear.from_weight(dev(torch, W), dev(torch, b), bits, 128, precision)
     assert lin.precision == precision and dllm._lib.load().dllm_linear_precision(lin._h) == precision
+    kernel = lin.plan(M).astuple()[0]   # the kernel that runs (dllm_linear_plan), not only the docstring's word
+    if M <= 64:
+        assert kernel == "DECODE"
+    elif precision == 1:
+        assert kernel == "ROUNDED_RING"
+    elif bits == 4 and N >= 512:
+        assert kernel == {(4096, 4096): "HORNER16", (4096, 4092): "HORNER16", (2048, 4096): "HORNER_PC",
+                          (2048, 4092): "HORNER_PC", (1800, 4096): "HORNER_PC", (4096, 1024): "HORNER_PC_KG2",
+                          (4096, 512): "HORNER_PC_KG2"}.get((M, N), "EXACT_FOLD"), (M, N, kernel)
+    else:
+        assert kernel == ("HORNER16" if (bits == 2 and M == 4096 and N >= 4092) else "EXACT_FOLD"), (M, N, kernel)
     ref = (X.astype(np.float64) @ W.astype(np.float64) + b).astype(np.float32)
     Xd = dev(torch, X).half()
     assert np.array_equal(host(lin(Xd, out_dtype=torch.float32)), ref)
@@ -513,11 +526,11 @@ def test_linear_horner_scale_spread(dllm, torch, orc, spread, M, K):
     """The 256 x 256-tile exact kernel (int4 g128, >= 256 tiles) keeps one accumulator in Horner form:
     acc <- acc * (s_{g-1} / s_g) + T_g, times s_{G-1} at the end; at M = 2048 / 3000 the same form
     runs on the producer/consumer 128 x 256 tiles, at M = 1024 / 1000 on the two-k-group 128 x 128
-    producer/consumer tiles (one chain per K-half), at M = 448 / 400 on their 64 x 128 form; at M =
-    1800 / 1850 (120 such tiles,
-    240 of the fold form's 128 x 256) the 256 x 128-tile KG2 kernel runs one chain per K-half (the
-    second starting from a zero accumulator) and sums the two halves' partials times their last
-    scales.  Per-(group, column) weight
+    producer/consumer tiles (one chain per K-half), at M = 448 / 400 on their 64 x 128 form; M =
+    1800 / 1850 (240 of the 128 x 256 tiles, short of a round) and M = 4300 also take the
+    producer/consumer 128 x 256 tiles (the 256 x 128-tile KG2 kernel that once ran at M 1793..1920 is
+    no longer reached at N 4096: tests/test_gpu_linear_kernels.py runs it where it is).  Per-(group,
+    column) weight
     magnitudes spread by 2^U(-spread, spread): every column is checked on its own against f32 on the
     same f16 X with the reference's a2 weights (quantization.rs:81-85), so a group rescaled wrongly
     shows even where other groups dominate the column.  spread 45 gives columns whose scales span
@@ -530,6 +543,10 @@ def test_linear_horner_scale_spread(dllm, torch, orc, spread, M, K):
     W = 0.02 * torch.randn(K, N, device="cuda", generator=g) * mult.repeat_interleave(128, 0)
     X = torch.randn(M, K, device="cuda", generator=g).half()
     lin = dllm.QuantLinear.from_weight(W, None, 4, 128)
+    want = ("EXACT_FOLD" if spread == 45 else
+            "HORNER16" if M in (4096, 8000, 3000) else
+            "HORNER_PC" if M in (4300, 1800, 1850, 2048) else "HORNER_PC_KG2")
+    assert lin.plan(M).astuple()[0] == want, (spread, M, K, lin.plan(M))
     base = 2 * K * N // 2 + G * N * 8 + N * 4        # code layouts, sz + sf, bias
     assert lin.device_bytes() == base + (0 if spread == 45 else (G + 1) * N * 4), (spread, lin.device_bytes())
     codes, scales, zps = lin.export()
@@ -652,7 +669,7 @@ def test_linear_decode_first_call_in_capture(dllm, torch):
 @pytest.mark.parametrize("M", [4096, 1800])
 def test_linear_horner_first_call_in_capture(dllm, torch, orc, M):
     """The forward contract: a handle's first call on a Horner grid (K = N = 4096, int4 g128; M 4096:
-    256 x 256 tiles, M 1800: the KG2 256 x 128 tiles) made inside stream capture runs the same
+    256 x 256 tiles, M 1800: the producer/consumer 128 x 256 tiles) made inside stream capture runs the same
     kernel as every later eager call -- the Horner ratios were decided at create, nothing is
     allocated or synchronised by the call -- so the graph replay and two eager calls are
     bit-identical, within the exact-weights bound of f32 on the same f16 X."""
@@ -661,6 +678,7 @@ def test_linear_horner_first_call_in_capture(dllm, torch, orc, M):
     W = 0.02 * torch.randn(K, N, device="cuda", generator=g)
     X = torch.randn(M, K, device="cuda", generator=g).half()
     lin = dllm.QuantLinear.from_weight(W, None, 4, 128)
+    assert lin.plan(M).astuple()[0] == {4096: "HORNER16", 1800: "HORNER_PC"}[M]
     before = lin.device_bytes()
     codes, scales, zps = lin.export()
     Wh = dev(torch, orc.dequantize_weights(orc.unpack_bits(host(codes), K * N, 4).reshape(K, N), host(scales),
