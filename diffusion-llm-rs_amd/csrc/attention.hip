@@ -9,8 +9,9 @@
 // so only the exact integers (q - z) are staged (exact in f16) and the scales fold into the softmax
 // exponent and the final normalisation: fewer roundings than dequantizing to f16 first.
 //
-// Layout: Q, O f16 [S][H][D]; K, V codes in the canonical packed bitstream of the flattened
-// [S][H][D] tensor (one per-tensor {scale, zp} pair each, on the device), D = 128.
+// Layout: Q, O f16 [Sq][H][D]; K, V codes of any width 1..8 in the canonical packed bitstream of the
+// flattened [Skv][H][D] tensor (one per-tensor {scale, zp} pair each, on the device), D = 128; or
+// K, V f32 (the cache's width-0 state), staged as f16 x 2^-e with the scale 2^e (kv_stage_f32_kernel).
 // Workgroup = 8 waves = 256 queries of one head; every 64-key block of K and V is staged once in
 // LDS (K as [key][d], V transposed as [d][key]) and shared by the 8 waves.
 // Per wave (32 queries): S^T = K Q^T with 32x32x16 f16 MFMA (keys in registers, the query on the
@@ -93,6 +94,8 @@ template <int BITS>
 struct Raw {
     uint32_t w[BITS == 4 ? 4 : 8];
 };
+template <int BITS> constexpr bool kv_gen = BITS != 4 && BITS != 8;
+template <int BITS> constexpr int kVWords = (8 * BITS + 31) / 32;
 
 // 32-bit byte offsets through buffer resources: keys at or past S read as 0 (out of range, no
 // memory access) instead of being clamped, and no 64-bit address math per block.
@@ -129,13 +132,20 @@ __device__ __forceinline__ void load_raw(Raw<BITS> &r, __amdgpu_buffer_rsrc_t kr
 // Position of key k (0..15) within its 16-key group of the V image: bits 2 and 3 swapped.
 __host__ __device__ constexpr int kv_pos(int k) { return (k & 3) | ((k & 4) << 1) | ((k & 8) >> 1); }
 
-// Code c (0..7) of an 8-code group of the thread's raw words, as the f16 pair trick input.
-template <int BITS>
-__device__ __forceinline__ half2_t pair_qz(uint32_t lo_word_codes, int shift, half2_t nz) {
-    // (code_a at bit shift, code_b at bit shift + BITS) -> f16 pair (1024 + code) - (1024 + z)
-    const uint32_t m = (1u << BITS) - 1u;
-    const uint32_t a = (lo_word_codes >> shift) & m, b = (lo_word_codes >> (shift + BITS)) & m;
-    const uint32_t t = (a | (b << 16)) | 0x64006400u;
+// Code i of an LSB-first stream of BITS-bit codes held in dwords w[w0 ..] (w0, i compile-time constants after
+// unrolling): a field that straddles a dword boundary (BITS 3, 5, 6, 7) takes its high part from the
+// next dword.  For BITS 4 and 8 this is the one-word shift and mask it always was.
+template <int BITS, int N>
+__device__ __forceinline__ uint32_t code_at(const uint32_t (&w)[N], int w0, int i) {
+    const int p = i * BITS, j = w0 + (p >> 5), sh = p & 31;
+    uint32_t v = w[j] >> sh;
+    if (sh + BITS > 32) v |= w[j + 1] << (32 - sh);
+    return v & ((1u << BITS) - 1u);
+}
+// Codes i and i + 1 as the f16 pair (1024 + code) - (1024 + z): exact integers for every width.
+template <int BITS, int N>
+__device__ __forceinline__ half2_t pair_qz(const uint32_t (&w)[N], int w0, int i, half2_t nz) {
+    const uint32_t t = (code_at<BITS>(w, w0, i) | (code_at<BITS>(w, w0, i + 1) << 16)) | 0x64006400u;
     return __builtin_bit_cast(half2_t, t) + nz;   // exact
 }
 
@@ -146,45 +156,93 @@ __device__ __forceinline__ half2_t pair_qz(uint32_t lo_word_codes, int shift, ha
 // sit in one 16-B run.
 __host__ __device__ constexpr int kv_pos16(int k) { return 8 * ((k >> 2) & 3) + 4 * ((k >> 4) & 1) + (k & 3); }
 
+// The thread's unpacked share into the LDS tiles.  K: the 32 codes of w[0 ..] to bk[key][d0 .. d0 + 32).
+template <int BITS, int N>
+__device__ __forceinline__ void put_k(const uint32_t (&w)[N], _Float16 (&bk)[kKB][kKRow], int key, int d0, half2_t kz) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {   // 4 x 8 codes -> 4 x b128 stores
+        half8_t out;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int c = 8 * g + 2 * p;   // code index within the 32
+            const half2_t v = pair_qz<BITS>(w, 0, c, kz);
+            out[2 * p] = v[0];
+            out[2 * p + 1] = v[1];
+        }
+        *reinterpret_cast<half8_t *>(&bk[key][d0 + 8 * g]) = out;
+    }
+}
+// V: keys k4 .. k4 + 3, the 8 codes of key i in w[kVWords<BITS> i ..], to bvt[d0 .. d0 + 8)[key position].
 // VL16: the V image in kv_pos16 order (kv_attention16_kernel); else kv_pos (kv_attention5_kernel).
+template <int BITS, bool VL16, int N>
+__device__ __forceinline__ void put_v(const uint32_t (&w)[N], _Float16 (&bvt)[kD][kVRow], int k4, int d0, half2_t vz) {
+    _Float16 v[4][8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const half2_t x = pair_qz<BITS>(w, kVWords<BITS> * i, 2 * p, vz);
+            v[i][2 * p] = x[0];
+            v[i][2 * p + 1] = x[1];
+        }
+    // transposed, 4 consecutive keys of one dim per 8-B store, at the key position of the V
+    // image: keys 4..7 and 8..11 of every 16 swap places (kv_pos), so that the 8 keys a PV
+    // fragment lane needs (16 s + 4 hh + {0..3, 8..11}) sit in one 16-B run.
+    const int kp4 = VL16 ? (k4 & ~31) | kv_pos16(k4 & 31) : (k4 & ~15) | kv_pos(k4 & 15);
+#pragma unroll
+    for (int dd = 0; dd < 8; ++dd)
+        *reinterpret_cast<half4_t *>(&bvt[d0 + dd][kp4]) = half4_t{v[0][dd], v[1][dd], v[2][dd], v[3][dd]};
+}
+
 template <int BITS, bool VL16 = false>
 __device__ __forceinline__ void store_raw(const Raw<BITS> &r, _Float16 (&bk)[kKB][kKRow], _Float16 (&bvt)[kD][kVRow],
                                           int tid, half2_t kz, half2_t vz) {
-    constexpr int CPW = 32 / BITS;   // codes per word
+    if (tid < 256) {
+        put_k<BITS>(r.w, bk, tid >> 2, 32 * (tid & 3), kz);
+    } else {
+        const int t = tid - 256;
+        put_v<BITS, VL16>(r.w, bvt, 4 * (t >> 4), 8 * (t & 15), vz);
+    }
+}
+
+// The widths without a power-of-two code (1, 2, 3, 5, 6, 7): the same thread ownership and tiles,
+// loaded and unpacked per branch.  A (key, head) row is 16 BITS bytes, so the K thread's 32 codes
+// are BITS whole dwords; the V thread's 8 codes of a key are BITS bytes at a byte offset that is
+// not dword-aligned for odd BITS: it loads the covering aligned dwords and funnel-shifts them down
+// to bit 0.  Every load stays a range-checked buffer load (a key at or past S reads 0 with no
+// memory access); a covering dword that the shift does not need may lie past the row or the
+// tensor: its bits are shifted out.
+template <int BITS>
+__device__ __forceinline__ void stage_gen(__amdgpu_buffer_rsrc_t krs, __amdgpu_buffer_rsrc_t vrs, _Float16 (&bk)[kKB][kKRow],
+                                          _Float16 (&bvt)[kD][kVRow], int tid, int j0, int H, int h, half2_t kz,
+                                          half2_t vz) {
+    constexpr uint32_t kRowB = kD * BITS / 8;
     if (tid < 256) {
         const int key = tid >> 2, d0 = 32 * (tid & 3);
+        const uint32_t off = (static_cast<uint32_t>(j0 + key) * H + h) * kRowB + (tid & 3) * 4 * BITS;
+        uint32_t w[BITS + 1];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {   // 4 x 8 codes -> 4 x b128 stores
-            half8_t out;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int c = 8 * g + 2 * p;   // code index within the 32
-                const half2_t v = pair_qz<BITS>(r.w[c / CPW], BITS * (c % CPW), kz);
-                out[2 * p] = v[0];
-                out[2 * p + 1] = v[1];
-            }
-            *reinterpret_cast<half8_t *>(&bk[key][d0 + 8 * g]) = out;
-        }
+        for (int j = 0; j < BITS; ++j) w[j] = __builtin_amdgcn_raw_buffer_load_b32(krs, off + 4 * j, 0, 0);
+        w[BITS] = 0;
+        put_k<BITS>(w, bk, key, d0, kz);
     } else {
         const int t = tid - 256, k4 = 4 * (t >> 4), d0 = 8 * (t & 15);
-        _Float16 v[4][8];
+        constexpr int kSMax = (BITS & 1) ? 24 : (BITS & 2) ? 16 : 0;   // largest shift
+        constexpr int NW = (kSMax + 8 * BITS + 31) / 32, NN = kVWords<BITS>;
+        uint32_t w[4 * NN + 1];
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t off = (static_cast<uint32_t>(j0 + k4 + i) * H + h) * kRowB + (t & 15) * BITS;
+            const uint32_t a = off & ~3u, sh = 8 * (off & 3u);
+            uint32_t raw[NW + 1];
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int c = 2 * p;
-                const uint32_t word = (BITS == 4) ? r.w[i] : r.w[2 * i + (c / CPW)];
-                const half2_t x = pair_qz<BITS>(word, BITS * (c % CPW), vz);
-                v[i][2 * p] = x[0];
-                v[i][2 * p + 1] = x[1];
-            }
-        // transposed, 4 consecutive keys of one dim per 8-B store, at the key position of the V
-        // image: keys 4..7 and 8..11 of every 16 swap places (kv_pos), so that the 8 keys a PV
-        // fragment lane needs (16 s + 4 hh + {0..3, 8..11}) sit in one 16-B run.
-        const int kp4 = VL16 ? (k4 & ~31) | kv_pos16(k4 & 31) : (k4 & ~15) | kv_pos(k4 & 15);
+            for (int j = 0; j < NW; ++j) raw[j] = __builtin_amdgcn_raw_buffer_load_b32(vrs, a + 4 * j, 0, 0);
+            raw[NW] = 0;
 #pragma unroll
-        for (int dd = 0; dd < 8; ++dd)
-            *reinterpret_cast<half4_t *>(&bvt[d0 + dd][kp4]) = half4_t{v[0][dd], v[1][dd], v[2][dd], v[3][dd]};
+            for (int j = 0; j < NN; ++j) w[NN * i + j] = __builtin_amdgcn_alignbit(raw[j + 1], raw[j], sh);
+        }
+        w[4 * NN] = 0;
+        put_v<BITS, false>(w, bvt, k4, d0, vz);
     }
 }
 
@@ -204,9 +262,78 @@ __global__ void __launch_bounds__(512) kv_stage_kernel(const uint8_t *__restrict
     const int nbytes = static_cast<int>(static_cast<size_t>(S) * H * kD * BITS / 8);
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(Kq), 0, nbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(Vq), 0, nbytes, 0x00020000);
-    Raw<BITS> raw;
-    load_raw<BITS>(raw, krs, vrs, tid, kb * kKB, kb * kKB, H, h);
-    store_raw<BITS, VL16>(raw, tk, tv, tid, kz, vz);
+    if constexpr (kv_gen<BITS>) {
+        stage_gen<BITS>(krs, vrs, tk, tv, tid, kb * kKB, H, h, kz, vz);
+    } else {
+        Raw<BITS> raw;
+        load_raw<BITS>(raw, krs, vrs, tid, kb * kKB, kb * kKB, H, h);
+        store_raw<BITS, VL16>(raw, tk, tv, tid, kz, vz);
+    }
+    __syncthreads();
+    uint8_t *dst = img + (static_cast<size_t>(h) * nkb + kb) * kImg;
+    const uint4 *sk = reinterpret_cast<const uint4 *>(&tk[0][0]);
+    const uint4 *sv = reinterpret_cast<const uint4 *>(&tv[0][0]);
+    for (int i = tid; i < kKImg / 16; i += 512) reinterpret_cast<uint4 *>(dst)[i] = sk[i];
+    for (int i = tid; i < kVImg / 16; i += 512) reinterpret_cast<uint4 *>(dst + kKImg)[i] = sv[i];
+}
+
+// ---- the f32 state (bits 0: the cache's "no decode copy" state, K and V unquantized) ----
+// The images hold RNE_f16(x * 2^-e) with one power of two per tensor, e the integer that puts the
+// tensor's max |x| into [2^14, 2^15) (e = 0 for an all-zero tensor; clamped to [-126, 113], which
+// only a max |x| below 2^-112 reaches), and the attention kernel runs with params {2^e, 0}: the
+// scaling is exact, so the f16 rounding of the image is the only rounding of K and V.
+// red = {-min_K, max_K, -min_V, max_V} (dllm_kv_extremes); params = {2^eK, 0, 2^eV, 0}.
+__global__ void kv_f32_params_kernel(const float *__restrict__ red, float *__restrict__ params) {
+    const int t = threadIdx.x;
+    if (t >= 2) return;
+    const float amax = fmaxf(red[2 * t], red[2 * t + 1]);
+    int e = 0;
+    if (amax > 0.0f) {
+        (void)frexpf(amax, &e);   // amax = m 2^e, m in [0.5, 1)
+        e = min(max(e - 15, -126), 113);
+    }
+    params[2 * t] = ldexpf(1.0f, e);
+    params[2 * t + 1] = 0.0f;
+}
+
+// The stage pass for f32 K / V: the same thread ownership, LDS tiles and image as kv_stage_kernel
+// (K thread: one key's 32 dims = 128 B; V thread: 4 keys x 8 dims = 4 x 32 B), range-checked buffer
+// loads so that keys at or past S stage as 0 with no memory access.
+__global__ void __launch_bounds__(512) kv_stage_f32_kernel(const float *__restrict__ K, const float *__restrict__ V,
+                                                          const float *__restrict__ params, int S, int H, int nkb,
+                                                          uint8_t *__restrict__ img) {
+    __shared__ __attribute__((aligned(16))) _Float16 tk[kKB][kKRow];
+    __shared__ __attribute__((aligned(16))) _Float16 tv[kD][kVRow];
+    const int tid = threadIdx.x, kb = blockIdx.x, h = blockIdx.y;
+    const float kinv = 1.0f / params[0], vinv = 1.0f / params[2];   // exact: powers of two
+    const int nbytes = static_cast<int>(static_cast<size_t>(S) * H * kD * 4);
+    const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(K), 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(V), 0, nbytes, 0x00020000);
+    auto load8 = [](__amdgpu_buffer_rsrc_t rs, uint32_t off, float inv) {   // 8 floats -> 8 scaled halves
+        const float4 a = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
+        const float4 b = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 16, 0, 0));
+        const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        half8_t o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = static_cast<_Float16>(x[j] * inv);   // RNE
+        return o;
+    };
+    if (tid < 256) {
+        const int key = tid >> 2, d0 = 32 * (tid & 3);
+        const uint32_t off = (static_cast<uint32_t>(kb * kKB + key) * H + h) * (kD * 4) + d0 * 4;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) *reinterpret_cast<half8_t *>(&tk[key][d0 + 8 * g]) = load8(krs, off + 32 * g, kinv);
+    } else {
+        const int t = tid - 256, k4 = 4 * (t >> 4), d0 = 8 * (t & 15);
+        half8_t v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            v[i] = load8(vrs, (static_cast<uint32_t>(kb * kKB + k4 + i) * H + h) * (kD * 4) + d0 * 4, vinv);
+        const int kp4 = (k4 & ~15) | kv_pos(k4 & 15);   // as store_raw
+#pragma unroll
+        for (int dd = 0; dd < 8; ++dd)
+            *reinterpret_cast<half4_t *>(&tv[d0 + dd][kp4]) = half4_t{v[0][dd], v[1][dd], v[2][dd], v[3][dd]};
+    }
     __syncthreads();
     uint8_t *dst = img + (static_cast<size_t>(h) * nkb + kb) * kImg;
     const uint4 *sk = reinterpret_cast<const uint4 *>(&tk[0][0]);
@@ -261,9 +388,11 @@ constexpr bool kAttnBdma = DLLM_ATTN_BDMA != 0;
 template <int LAB = 0, bool STAG = false>
 __global__ void __launch_bounds__(kWaves * 64)
 kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__ img, const float *__restrict__ kp,
-                    const float *__restrict__ vp, int S, int H, _Float16 *__restrict__ O) {
+                    const float *__restrict__ vp, int Sq, int Skv, int H, _Float16 *__restrict__ O) {
+    // Sq query rows (the Q load clamp, the O store mask, the grid) against Skv keys (the image blocks,
+    // the last block's mask): a block of new tokens attends the whole cache.
     constexpr int NB = STAG ? 3 : 2;
-    const int nkb = (S + kKB - 1) / kKB;
+    const int nkb = (Skv + kKB - 1) / kKB;
     __shared__ __attribute__((aligned(16))) AttnSmemN<NB> sm;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = blockIdx.y;
@@ -276,7 +405,7 @@ kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__
     // Q^T fragments (B operand of S^T = K Q^T): lane holds Q[q = q0 + ql][d = 16 t + 8 hh + j].
     half8_t qf[kD / 16];
     {
-        const int qrow = min(q0 + ql, S - 1);
+        const int qrow = min(q0 + ql, Sq - 1);
         const _Float16 *qp = Q + (static_cast<size_t>(qrow) * H + h) * kD + 8 * hh;
 #pragma unroll
         for (int t = 0; t < kD / 16; ++t) qf[t] = *reinterpret_cast<const half8_t *>(qp + 16 * t);
@@ -392,14 +521,14 @@ kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__
                 }
             }
         }
-        if (__builtin_expect(j0 + kKB > S, 0)) {   // last, partial block only (a real branch)
+        if (__builtin_expect(j0 + kKB > Skv, 0)) {   // last, partial block only (a real branch)
             asm volatile("" ::: "memory");
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = j0 + 32 * u + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                    st[u][r] = key < S ? st[u][r] : -INFINITY;
+                    st[u][r] = key < Skv ? st[u][r] : -INFINITY;
                 }
         }
         // ---- region 1.  After the last block the K buffer is stale: sn is computed and dropped.
@@ -579,7 +708,7 @@ kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__
 #pragma unroll
         for (int it = 0; it < 8; ++it) {
             const int c = it * 64 + lane, r = c >> 4, cc = c & 15;
-            if (q0 + r < S)
+            if (q0 + r < Sq)
                 *reinterpret_cast<u32x4_t *>(O + (static_cast<size_t>(q0 + r) * H + h) * kD + 8 * cc) =
                     *reinterpret_cast<const u32x4_t *>(tile + r * kKRow + 8 * cc);
         }
@@ -592,7 +721,7 @@ kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int q = q0 + 8 * g + 4 * hh + i;
-            if (q >= S) continue;
+            if (q >= Sq) continue;
             _Float16 *op = O + (static_cast<size_t>(q) * H + h) * kD + ql;
 #pragma unroll
             for (int dt = 0; dt < kD / 32; ++dt) op[32 * dt] = static_cast<_Float16>(o[dt][4 * g + i] * iv[i]);
@@ -618,20 +747,31 @@ kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__
 using namespace dllm;
 
 
-extern "C" int dllm_kv_attention(const void *Q, const uint8_t *Kq, const float *k_params, const uint8_t *Vq,
-                                 const float *v_params, uint8_t bits, size_t S, size_t H, size_t D, void *O,
-                                 dllm_stream_t stream) {
-    if (D != kD) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention: head dim must be 128");
-    if (bits != 4 && bits != 8) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention: bits must be 4 or 8");
-    if (S == 0 || H == 0) return DLLM_OK;
-    if (!Q || !Kq || !Vq || !k_params || !v_params || !O) return fail(DLLM_ERR_INVALID_PARAMS, "null pointer");
-    if (S * H * D * bits / 8 >= (size_t{1} << 31) || H > 65535)
+namespace {
+
+template <int BITS>
+void launch_stage(dim3 sgrid, hipStream_t st, const uint8_t *Kq, const float *kp, const uint8_t *Vq, const float *vp,
+                  int Skv, int H, int nkb, uint8_t *img) {
+    kv_stage_kernel<BITS><<<sgrid, 512, 0, st>>>(Kq, kp, Vq, vp, Skv, H, nkb, img);
+}
+
+// Both entry points past their width checks.  bits 1..8: Kv / Vv are packed codes with device params;
+// bits 0: device f32 tensors, staged with the power-of-two params this call writes to its workspace.
+int kv_attention_launch(const void *Q, size_t Sq, const void *Kv, const float *k_params, const void *Vv,
+                        const float *v_params, uint8_t bits, size_t Skv, size_t H, void *O, dllm_stream_t stream) {
+    const size_t D = kD;
+    const uint8_t *Kq = static_cast<const uint8_t *>(Kv), *Vq = static_cast<const uint8_t *>(Vv);
+    if (Sq == 0 || H == 0) return DLLM_OK;
+    if (Skv == 0) return fail(DLLM_ERR_INVALID_PARAMS, "dllm_kv_attention: no keys (softmax over an empty set)");
+    if (!Q || !Kq || !Vq || (bits && (!k_params || !v_params)) || !O) return fail(DLLM_ERR_INVALID_PARAMS, "null pointer");
+    if ((bits ? Skv * H * D * bits / 8 : Skv * H * D * 4) >= (size_t{1} << 31) || H > 65535)
         return fail(DLLM_ERR_SHAPE_MISMATCH, "K/V codes must stay below 2 GiB (32-bit buffer offsets)");
+    if (Sq >= (size_t{1} << 31)) return fail(DLLM_ERR_SHAPE_MISMATCH, "too many query rows");
     if ((reinterpret_cast<uintptr_t>(Kq) & 15) || (reinterpret_cast<uintptr_t>(Vq) & 15) ||
         (reinterpret_cast<uintptr_t>(Q) & 15) || (reinterpret_cast<uintptr_t>(O) & 15))
         return fail(DLLM_ERR_INVALID_PARAMS, "Q, O, K and V codes must be 16-byte aligned");   // O: 16-B row stores
     hipStream_t st = as_stream(stream);
-    const int nkb = static_cast<int>((S + kKB - 1) / kKB);
+    const int nkb = static_cast<int>((Skv + kKB - 1) / kKB);
     // the attention kernel stages a head's f16 K / V images through one buffer descriptor with
     // 32-bit offsets (blk * kImg): a head's images must stay below 2 GiB too (~560 B per key, so
     // S past ~3.8 M keys at small H would pass the code-size check above)
@@ -641,18 +781,45 @@ extern "C" int dllm_kv_attention(const void *Q, const uint8_t *Kq, const float *
     if (!img) return DLLM_ERR_HIP;
     dim3 sgrid(static_cast<unsigned>(nkb), static_cast<unsigned>(H));
 #if DLLM_LAB
-    const int lab = [] { const char *e = getenv("DLLM_ATTN_LAB"); return e ? atoi(e) : 0; }();
+    // The A/B schedules are single-S kernels fed by the 4- and 8-bit stage pass: every other width and
+    // every Sq != Skv call runs the product kernel.
+    const int lab = (Sq == Skv && (bits == 4 || bits == 8))
+                        ? [] { const char *e = getenv("DLLM_ATTN_LAB"); return e ? atoi(e) : 0; }() : 0;
+#endif
+    if (bits == 0) {
+        // The f32 state: max |x| of K and of V (dllm_kv_extremes, one launch for both, the result
+        // stays on the device), the params {2^e, 0} from them, then the scaled f16 images.  Slot 9:
+        // params[4], red[4], then the extremes' partials.
+        const size_t n = Skv * H * D, part = dllm_quantize_kv_workspace(n, n);
+        float *aux = device_workspace(st, 32 + part, 9);
+        if (!aux) return DLLM_ERR_HIP;
+        const float *Kf = static_cast<const float *>(Kv), *Vf = static_cast<const float *>(Vv);
+        const int rc = dllm_kv_extremes(Kf, n, Vf, n, aux + 4, aux + 8, part, stream);
+        if (rc) return rc;
+        kv_f32_params_kernel<<<1, 64, 0, st>>>(aux + 4, aux);
+        DLLM_LAUNCH_CHECK();
+        kv_stage_f32_kernel<<<sgrid, 512, 0, st>>>(Kf, Vf, aux, (int)Skv, (int)H, nkb, img);
+        k_params = aux;
+        v_params = aux + 2;
+    } else
+#if DLLM_LAB
     if (lab == 16) {   // the 16x16x32 kernel (A/B): its V image in kv_pos16 order
-        if (bits == 4) kv_stage_kernel<4, true><<<sgrid, 512, 0, st>>>(Kq, k_params, Vq, v_params, (int)S, (int)H, nkb, img);
-        else kv_stage_kernel<8, true><<<sgrid, 512, 0, st>>>(Kq, k_params, Vq, v_params, (int)S, (int)H, nkb, img);
+        if (bits == 4) kv_stage_kernel<4, true><<<sgrid, 512, 0, st>>>(Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img);
+        else kv_stage_kernel<8, true><<<sgrid, 512, 0, st>>>(Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img);
     } else
 #endif
-    if (bits == 4)
-        kv_stage_kernel<4><<<sgrid, 512, 0, st>>>(Kq, k_params, Vq, v_params, (int)S, (int)H, nkb, img);
-    else
-        kv_stage_kernel<8><<<sgrid, 512, 0, st>>>(Kq, k_params, Vq, v_params, (int)S, (int)H, nkb, img);
+    switch (bits) {
+        case 1: launch_stage<1>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 2: launch_stage<2>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 3: launch_stage<3>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 4: launch_stage<4>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 5: launch_stage<5>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 6: launch_stage<6>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 7: launch_stage<7>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        default: launch_stage<8>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+    }
     DLLM_LAUNCH_CHECK();
-    dim3 grid(static_cast<unsigned>((S + kQT - 1) / kQT), static_cast<unsigned>(H));
+    dim3 grid(static_cast<unsigned>((Sq + kQT - 1) / kQT), static_cast<unsigned>(H));
     const _Float16 *Qh = static_cast<const _Float16 *>(Q);
     _Float16 *Oh = static_cast<_Float16 *>(O);
 #if DLLM_LAB
@@ -663,47 +830,66 @@ extern "C" int dllm_kv_attention(const void *Q, const uint8_t *Kq, const float *
     // results); 200 (+ mask): v6.  Read per call so that a script can A/B the schedules in one process.
     switch (lab) {
         case 16:   // the 16x16x32 kernel (A/B)
-            kv_attention16_kernel<<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh);
+            kv_attention16_kernel<<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Skv, (int)H, Oh);
             break;
-#define DLLM_ALAB(L) case L: kv_attention_kernel<L><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh); break;
+#define DLLM_ALAB(L) case L: kv_attention_kernel<L><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Skv, (int)H, Oh); break;
         DLLM_ALAB(1) DLLM_ALAB(2) DLLM_ALAB(3) DLLM_ALAB(4) DLLM_ALAB(5) DLLM_ALAB(6) DLLM_ALAB(7)
         DLLM_ALAB(8) DLLM_ALAB(12) DLLM_ALAB(13) DLLM_ALAB(14) DLLM_ALAB(15)
 #undef DLLM_ALAB
         case 100:   // the v4 schedule (A/B)
-            kv_attention_kernel<0><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh);
+            kv_attention_kernel<0><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Skv, (int)H, Oh);
             break;
-#define DLLM_ALAB5(L) case 100 + L: kv_attention5_kernel<L><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh); break;
+#define DLLM_ALAB5(L) case 100 + L: kv_attention5_kernel<L><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh); break;
         DLLM_ALAB5(1) DLLM_ALAB5(2) DLLM_ALAB5(4) DLLM_ALAB5(8) DLLM_ALAB5(12) DLLM_ALAB5(13) DLLM_ALAB5(3) DLLM_ALAB5(16)
         DLLM_ALAB5(48) DLLM_ALAB5(50) DLLM_ALAB5(64) DLLM_ALAB5(128)
 #undef DLLM_ALAB5
         case 200:   // v6: 4 waves x 64 queries (A/B)
-            kv_attention6_kernel<0><<<grid, kW6 * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh);
+            kv_attention6_kernel<0><<<grid, kW6 * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Skv, (int)H, Oh);
             break;
-#define DLLM_ALAB6(L) case 200 + L: kv_attention6_kernel<L><<<grid, kW6 * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh); break;
+#define DLLM_ALAB6(L) case 200 + L: kv_attention6_kernel<L><<<grid, kW6 * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Skv, (int)H, Oh); break;
         DLLM_ALAB6(2) DLLM_ALAB6(4) DLLM_ALAB6(8)
 #undef DLLM_ALAB6
         case 302:   // the product without the region-2 priority (A/B; bit-identical)
-            kv_attention5_kernel<256, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh);
+            kv_attention5_kernel<256, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
             break;
         case 4196:   // the product with the round-2 epilogue, 64 two-byte stores per lane (A/B; bit-identical)
-            kv_attention5_kernel<4096, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh);
+            kv_attention5_kernel<4096, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
             break;
         case 612:   // the product without the region-1 softmax pins (A/B; bit-identical)
-            kv_attention5_kernel<512, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh);
+            kv_attention5_kernel<512, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
             break;
         case 700:   // the producer/consumer kernel (A/B; bit-identical)
-            kv_attention_pc_kernel<<<grid, kPcAttnWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh);
+            kv_attention_pc_kernel<<<grid, kPcAttnWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Skv, (int)H, Oh);
             break;
         case 198:   // the staggered schedule (A/B; bit-identical)
-            kv_attention5_kernel<0, true><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh);
+            kv_attention5_kernel<0, true><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
             break;
         default:
-            kv_attention5_kernel<0, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh);
+            kv_attention5_kernel<0, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
             break;
     }
 #else
-    kv_attention5_kernel<0, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)S, (int)H, Oh);
+    kv_attention5_kernel<0, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
 #endif
     DLLM_LAUNCH_CHECK();
     return DLLM_OK;
+}
+
+}  // namespace
+
+extern "C" int dllm_kv_attention_ex(const void *Q, size_t Sq, const void *K, const float *k_params, const void *V,
+                                    const float *v_params, uint8_t bits, size_t Skv, size_t H, size_t D, void *O,
+                                    dllm_stream_t stream) {
+    if (D != kD) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention_ex: head dim must be 128");
+    if (bits > 8) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention_ex: bits must be 0 (f32 K/V) or 1..8");
+    return kv_attention_launch(Q, Sq, K, k_params, V, v_params, bits, Skv, H, O, stream);
+}
+
+// The Sq == Skv == S, bits in {4, 8} case of the same launcher (its refusals as they always were).
+extern "C" int dllm_kv_attention(const void *Q, const uint8_t *Kq, const float *k_params, const uint8_t *Vq,
+                                 const float *v_params, uint8_t bits, size_t S, size_t H, size_t D, void *O,
+                                 dllm_stream_t stream) {
+    if (D != kD) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention: head dim must be 128");
+    if (bits != 4 && bits != 8) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention: bits must be 4 or 8");
+    return kv_attention_launch(Q, S, Kq, k_params, Vq, v_params, bits, S, H, O, stream);
 }

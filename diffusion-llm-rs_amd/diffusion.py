@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .quantization import QuantizedKVCacheEntry
+from .quantization import QuantizedKVCacheEntry, kv_attention
 
 
 class BetaSchedule(IntEnum):
@@ -204,6 +204,20 @@ class KVCacheEntry:
     def _dequantize(self, t):
         """QuantizedKVCacheEntry::dequantize_keys/values (quantization.rs:160-175)."""
         return t.dequantize().reshape(t.shape)
+
+    def attention(self, q: torch.Tensor, layer: int = 0) -> torch.Tensor:
+        """Dequant-attention of ``q`` f16 [Sq, H, 128] (H * 128 == hidden) to layer ``layer``'s K/V
+        in the state the entry is in -- the data ``get_keys()[layer]`` / ``get_values()[layer]``
+        hand out: the prefill copy, the decode copy at its current progressive width, or the f32
+        tensors when there is no copy (width 0) -- read in place, nothing dequantized to HBM."""
+        cur = self._current()
+        k, v = (self.keys, self.values) if cur is None else (cur.keys, cur.values)
+        layers, seq, hidden = (int(d) for d in k.shape)
+        if q.dim() != 3 or int(q.shape[1]) * int(q.shape[2]) != hidden:
+            raise _lib.ShapeMismatch("q must be [Sq, H, D] with H * D == the cache's hidden size")
+        if not 0 <= layer < layers:
+            raise _lib.InvalidParams(f"layer {layer} out of range (the cache holds {layers})")
+        return kv_attention(q, k, v, offset=layer * seq * hidden, skv=seq)
 
     def get_current_quant_bits(self) -> int:
         return self.prefill_quant_bits if self.is_prefill_phase else self.decode_quant_bits

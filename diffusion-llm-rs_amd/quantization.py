@@ -371,22 +371,51 @@ class QuantizedKVCacheEntry:
         return sum(packed_bytes(t.numel(), t.bits) for t in (self.keys, self.values))
 
 
-def kv_attention(q: torch.Tensor, keys: QuantizedTensor, values: QuantizedTensor) -> torch.Tensor:
-    """Quantized-KV dequant-attention (a9): O = softmax(Q K^T / sqrt(D)) V per head with K, V the
-    per-tensor quantized cache tensors of ``QuantizedKVCacheEntry`` (packed, 4 or 8 bits),
-    dequantized inside the kernel.  q: f16 [S, H, 128] -> O f16 [S, H, 128]."""
+def kv_attention(q: torch.Tensor, keys, values, *, offset: int = 0, skv: int | None = None) -> torch.Tensor:
+    """KV dequant-attention (a9, dllm_kv_attention_ex): O = softmax(Q K^T / sqrt(D)) V per head, q f16
+    [Sq, H, 128] -> O f16 [Sq, H, 128], against all Skv keys of a cache in any of its states:
+
+    * ``keys`` / ``values`` packed :class:`QuantizedTensor` of one width 1..8 (the per-tensor
+      quantized copies of ``QuantizedKVCacheEntry``), dequantized inside the kernel, or
+    * f32 device tensors (the cache's "no decode copy" state), staged as f16 with one power-of-two
+      scale per tensor (include/dllm_quant.h).
+
+    K and V are the ``[Skv, H, 128]`` elements ``offset .. offset + Skv * H * 128`` of the flattened
+    tensors, read in place: ``offset = layer * seq * hidden, skv = seq`` addresses one layer of a
+    ``[layers, seq, hidden]`` cache tensor.  By default Skv is every whole row from ``offset`` on.
+    The slice must start on a 16-byte boundary of the code stream (any layer of a cache does)."""
     if q.dim() != 3:
         raise _lib.ShapeMismatch("q must be [S, H, D]")
-    S, H, D = q.shape
-    for t in (keys, values):
-        if not t.packed or t.numel() != S * H * D:
-            raise _lib.ShapeMismatch("keys/values must be packed [S, H, D] QuantizedTensors")
-    if keys.bits != values.bits:
-        raise _lib.InvalidParams("keys and values must share the bit width")
+    Sq, H, D = q.shape
+    f32 = isinstance(keys, torch.Tensor)
+    if f32 != isinstance(values, torch.Tensor):
+        raise _lib.InvalidParams("keys and values must both be quantized or both be f32 tensors")
+    if f32:
+        keys, values = _dev(keys, torch.float32), _dev(values, torch.float32)
+        bits, kd, vd, kp, vp = 0, keys, values, None, None
+    else:
+        if not (keys.packed and values.packed):
+            raise _lib.ShapeMismatch("keys/values must be packed QuantizedTensors")
+        if keys.bits != values.bits:
+            raise _lib.InvalidParams("keys and values must share the bit width")
+        bits, kd, vd, kp, vp = int(keys.bits), keys.data, values.data, keys.params, values.params
+    n, row, offset = keys.numel(), H * D, int(offset)
+    if values.numel() != n:
+        raise _lib.ShapeMismatch("keys and values must have the same number of elements")
+    if skv is None:
+        if offset < 0 or offset > n or row == 0 or (n - offset) % row:
+            raise _lib.ShapeMismatch("keys/values past `offset` must be whole [H, D] rows of q's H and D")
+        skv = (n - offset) // row
+    elif offset < 0 or skv < 0 or offset + skv * row > n:
+        raise _lib.ShapeMismatch("keys/values hold fewer than offset + skv * H * D elements")
+    byte_off = offset * (bits or 32)
+    if byte_off % 128:
+        raise _lib.InvalidParams("the K/V slice must start on a 16-byte boundary of the code stream")
+    byte_off //= 8
     qd = _dev(q, torch.float16)
-    out = torch.empty(S, H, D, dtype=torch.float16, device=qd.device)
-    check(_lib.load().dllm_kv_attention(_ptr(qd), _ptr(keys.data), _ptr(keys.params), _ptr(values.data),
-                                        _ptr(values.params), keys.bits, S, H, D, _ptr(out), _stream()))
+    out = torch.empty(Sq, H, D, dtype=torch.float16, device=qd.device)
+    check(_lib.load().dllm_kv_attention_ex(_ptr(qd), Sq, kd.data_ptr() + byte_off, _ptr(kp), vd.data_ptr() + byte_off,
+                                           _ptr(vp), bits, skv, H, D, _ptr(out), _stream()))
     return out
 
 

@@ -373,6 +373,31 @@ int dllm_compressed_vector_from_json(const char *s, size_t len, char *id, size_t
 int dllm_kv_attention(const void *Q, const uint8_t *Kq, const float *k_params, const uint8_t *Vq,
                       const float *v_params, uint8_t bits, size_t S, size_t H, size_t D, void *O,
                       dllm_stream_t stream);
+/* The same consumer for every state of the phase-aware cache (KVCacheEntry, diffuse-llm-rs/src/lib.rs:121-313)
+ * and for a block of Sq query tokens against a cache of Skv keys: Q, O f16 [Sq][H][D], K, V [Skv][H][D],
+ * O = softmax(Q K^T / sqrt(D)) V per head over all Skv keys (bidirectional, no mask), D == 128.
+ *   bits 1..8  K, V = canonical packed LSB-first code streams of the flattened [Skv][H][D] tensor
+ *              (a1 layout; may point into a larger stream, e.g. one layer of [layers][seq][hidden],
+ *              at any 16-byte-aligned byte offset) with device params {scale, zp} each.
+ *   bits 0     K, V = device f32 [Skv][H][D]: the cache's "no decode copy" state (progressive width
+ *              0, lib.rs:190-197).  k_params / v_params are ignored and may be NULL.  Staging rule:
+ *              per tensor amax = max |x| (NaN-ignoring extremes, on the device, no host read); e = the
+ *              integer with amax * 2^-e in [2^14, 2^15) (0 when amax == 0, clamped to [-126, 113]); the
+ *              kernel computes with RNE_f16(x * 2^-e) and the scale 2^e, so the f16 rounding of
+ *              x * 2^-e is the only rounding of K and V.  Non-finite K / V are NOT checked (a check
+ *              would need a host sync); the result is then unspecified.
+ *   bits > 8 -> DLLM_ERR_UNSUPPORTED.  Sq == 0 or H == 0 -> DLLM_OK, nothing written; Skv == 0 with
+ *   Sq > 0 -> DLLM_ERR_INVALID_PARAMS (softmax over no keys).  Null pointers, Q / O / K / V not
+ *   16-byte aligned -> DLLM_ERR_INVALID_PARAMS; K or V of 2 GiB or more (4 bytes per element for
+ *   bits 0) -> DLLM_ERR_SHAPE_MISMATCH.
+ * Asynchronous on `stream`, never synchronises.  The only allocations are the grow-only per-stream
+ * workspaces (the images, H * ceil(Skv/64) * 35 KiB; for bits 0 also a few KiB for the extremes and
+ * the params), made on the first call of a shape: capture-safe once a shape has run.
+ * dllm_kv_attention is the Sq == Skv == S, bits in {4, 8} case of the same launcher and refuses
+ * every other width as it always did. */
+int dllm_kv_attention_ex(const void *Q, size_t Sq, const void *K, const float *k_params, const void *V,
+                         const float *v_params, uint8_t bits, size_t Skv, size_t H, size_t D, void *O,
+                         dllm_stream_t stream);
 
 /* ---- 8f rank 1: diffusion-step ops either side of the denoiser --------------------------------
  * DiffuseLLM's schedule and sampling step (diffuse-llm-rs/src/lib.rs).  Host functions compute the
