@@ -61,8 +61,8 @@ kv_attention_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__ 
         const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_addr(&sm.vt[buf][0][0]));
         for (uint32_t p = p0 == 0xffffffffu ? wv : p0; p < kVImg / 1024; p += step) glds16_asm(src + p * 1024, dst + p * 1024);
     };
-    const bool grp_b = STAG && wave >= kWaves / 2;
-    auto raw_barrier = []() __attribute__((always_inline)) {
+    [[maybe_unused]] const bool grp_b = STAG && wave >= kWaves / 2;
+    [[maybe_unused]] auto raw_barrier = []() __attribute__((always_inline)) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);

@@ -23,14 +23,24 @@ void launch_horner_t(const HornerGemmArgs &a, int y_f32, hipStream_t st, int gro
 }
 
 int launch_horner_lab(const HornerGemmArgs &a, int y_f32, hipStream_t st) {
-    if (a.lab == 44 || a.lab == 45) {   // lab: the product without stores (44, timing only) / with the
+    if (a.lab >= 46 && a.lab <= 48) {   // lab A/B (bit-identical): the 4-slot ring in lockstep (46) / with the
+                                        // skew (47), the 3-slot two-barrier ring (48)
+        if (a.lab == 46) launch_horner16_t<kH16Ring4>(a, y_f32, st);
+        else if (a.lab == 47) launch_horner16_t<kH16Ring4Skew>(a, y_f32, st);
+        else launch_horner16_t<kH16Ring3>(a, y_f32, st);
+        DLLM_LAUNCH_CHECK();
+        return DLLM_OK;
+    }
+    // (Variants 40..45 below instantiate the 3-slot two-barrier schedule, kH16Ring3: the product kernel
+    // until the 4-slot ring, lab 48 today.  The 4-slot ring excludes MODE bits 3 and 6.)
+    if (a.lab == 44 || a.lab == 45) {   // lab: the 3-slot schedule without stores (44, timing only) / with the
         // 8-B register stores instead of the LDS-staged 16-B rows (45, bit-identical)
         if (a.lab == 44) launch_horner16_t<1 | 256 | 1024 | 2>(a, y_f32, st);
         else launch_horner16_t<1 | 256 | 1024 | 4096>(a, y_f32, st);
         DLLM_LAUNCH_CHECK();
         return DLLM_OK;
     }
-    if (a.lab >= 40 && a.lab <= 43) {   // lab ablations of the product kernel (variants 340..343; results
+    if (a.lab >= 40 && a.lab <= 43) {   // lab ablations of the 3-slot schedule (variants 340..343; results
         // wrong, timing only): 40 no Horner rescale, 41 no rescale and the A fragments built once (no
         // dequant VALU in the loop), 42 no DMA after the prologue, 43 MFMAs + LDS reads + barriers only
         // (41 + 42, no stores)

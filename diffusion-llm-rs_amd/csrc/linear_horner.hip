@@ -14,8 +14,12 @@
 // consecutive columns): block 256 tokens x 256 columns, 8 waves side by side in n (2 per SIMD),
 // wave tile 32 columns x 256 tokens (acc = 8 x 16 f32).  Per 64-deep k-step a stage holds the X
 // tile (32 KiB, XOR-swizzled 16-B chunks), the 8 waves' weight words (8 KiB) and, on a group's
-// first k-step, the group's {zp, scale} pairs and ratios (2 KiB); 3 stages in a ring, stage kt+2
-// issued while kt computes, one counted vmcnt wait and one raw s_barrier per k-step.
+// first k-step, the group's {zp, scale} pairs and ratios (2 KiB); stage kt+2 issued while kt
+// computes, counted vmcnt waits and raw s_barriers.  The 256-token product schedule (MODE bit 13 of
+// wq_horner16_kernel) keeps the X tile and the group data in 4 ring slots of 34 KiB and each wave's
+// weight words in a ring of its own (3 x 1 KiB per wave; 160 KiB in all): one s_barrier per k-step,
+// waves 4-7 half a k-step behind in program order.  The 128-token tiles and the lab arms keep the
+// 3-slot ring (words inside the slots) with a barrier every half k-step.
 //
 // Against wq_gemm8_kernel<..., HORNER> (linear_wq.hip, the same arithmetic and schedule, bit for bit)
 // this kernel cuts the instruction stream around the MFMAs, which two waves per SIMD must share:
@@ -69,7 +73,9 @@ __device__ __forceinline__ void horner_burst(__amdgpu_buffer_rsrc_t xr, uint32_t
         : "memory");
 }
 
-// (wq_horner16_kernel: MODE bit 10 = half 1's A fragments built right after substep 1 (product);
+// (wq_horner16_kernel: MODE bit 13 = the 4-slot ring with one barrier per k-step (TB = 16; product
+// with bit 0, where bit 0 then means the skew of waves 4-7 in program order; see the schedule's
+// comment in the kernel).  MODE bit 10 = half 1's A fragments built right after substep 1 (product);
 // bit 11 = a non-group-first step's words and half-0 A fragments built at the end of the step
 // before (lab A/B 325, not adopted).)
 // MODE bit 0: the staggered schedule (product).  Lab ablations only (results wrong, timing only):
@@ -498,8 +504,16 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
     // stage's bytes) and reads its own half, so the ring, the pieces per stage and the waits are int4's.
     static_assert(BITS == 4 || (BITS == 2 && TB == 16), "int4, or int2 on 256-token tiles");
     using L = H16<TB>;
-    constexpr int kStage = L::kStage, kXB = L::kXB, kKPS = L::kKPS;
-    __shared__ __attribute__((aligned(16))) uint8_t smem[3 * kStage];
+    constexpr bool RING4 = (MODE & 8192) != 0;
+    static_assert(!RING4 || (TB == 16 && (MODE & (256 | 1024)) == (256 | 1024) && (MODE & (2048 | 64 | 8)) == 0),
+                  "the 4-slot ring: 256-token tiles, spread pieces, half 1's A fragments after substep 1");
+    // RING4: a slot holds X and the group data only (34 KiB); the weight words live in a wave-private
+    // ring of 3 x 1 KiB per wave behind the 4 slots (4 x 34 + 24 = 160 KiB).
+    constexpr int kXB = L::kXB, kKPS = L::kKPS;
+    constexpr int kStage = RING4 ? kXB + kHG : L::kStage;
+    constexpr int kGOff = RING4 ? kXB : kXB + L::kWB;        // the group data within a slot
+    constexpr int kWRing = 4 * (kXB + kHG);                  // RING4: the private word rings
+    __shared__ __attribute__((aligned(16))) uint8_t smem[RING4 ? kWRing + 8 * 3 * 1024 : 3 * kStage];
 
     // XCD-aware bijective remap (as wq_horner_kernel)
     const int nb = nbm * nbn, orig = blockIdx.x;
@@ -529,13 +543,27 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
         raw_rsrc(wave == 0 ? static_cast<const void *>(sz + n0) : static_cast<const void *>(hr + n0));
     const bool has_g = wave < 2;
     const uint32_t sbase = __builtin_amdgcn_readfirstlane(lds_addr(smem));
+    // RING4: the group's 2 KiB ({zp, scale} 1 KiB, ratios 1 KiB) as 8 pieces of 256 B, one per wave
+    const __amdgpu_buffer_rsrc_t gr4 = raw_rsrc(wave < 4 ? static_cast<const void *>(sz + n0 + 64 * wave)
+                                                         : static_cast<const void *>(hr + n0 + 64 * (wave - 4)));
+    // RING4: byte offsets within the wave's word ring of the k-step being read (k-step % 3) and of
+    // the stage being issued (two k-steps ahead)
+    uint32_t wq = 0, wq_iss = 2048;
 
     // DMA piece p of stage st into ring slot `slot`: X pieces (sub-tile p / kNX, piece p % kNX), then
     // the weight words of each k-step, then (group-first stages, waves 0 and 1) the group data.
     auto piece = [&](int p, int slot, int st, bool gf) __attribute__((always_inline)) {
         const uint32_t base = sbase + static_cast<uint32_t>(slot * kStage);
         constexpr int nxp = kKPS * L::kNX;
-        if (p < nxp) {
+        if constexpr (RING4) {   // every wave: 4 X pieces, its words, (group-first stages) 256 B of group data
+            if (p < 4)
+                blds16_asm(xr, xo[p], static_cast<uint32_t>(st * kBK * 2), base + static_cast<uint32_t>(wave * 1024 + p * 0x2000));
+            else if (p == 4)
+                blds16_asm(wr, wo, wsoff(st), sbase + static_cast<uint32_t>(kWRing + wave * 3072) + wq_iss);
+            else if (p == 5 && gf)
+                blds4_asm(gr4, static_cast<uint32_t>(lane * 4), static_cast<uint32_t>((st >> 1) * Npad * 4),
+                          base + static_cast<uint32_t>(kXB + wave * 256));
+        } else if (p < nxp) {
             const int kk = p / L::kNX, i = p % L::kNX;
             blds16_asm(xr, xo[i], static_cast<uint32_t>((st * kKPS + kk) * kBK * 2),
                        base + static_cast<uint32_t>(kk * L::kXSub + wave * 1024 + i * 0x2000));
@@ -593,7 +621,16 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
     half8_t bA[8], bB[8], a00, a01, a10, a11;
     // par: the k-step's parity (BITS = 2: which half of the pair's piece)
     auto load_w = [&](const uint8_t *sb, int kk, int par) __attribute__((always_inline)) {
-        if constexpr (BITS == 4) {
+        if constexpr (RING4) {   // the wave's own ring: ordered by its own vmcnt wait alone
+            const uint8_t *wp = smem + kWRing + wave * 3072 + wq;
+            if constexpr (BITS == 4) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(wp + lane * 16);
+                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+            } else {
+                const uint2 v = *reinterpret_cast<const uint2 *>(wp + par * 512 + lane * 8);
+                w[0] = v.x; w[1] = v.y;
+            }
+        } else if constexpr (BITS == 4) {
             (void)par;
             const uint4 v = *reinterpret_cast<const uint4 *>(sb + kXB + kk * kHW + wave * 1024 + lane * 16);
             w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
@@ -744,9 +781,9 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
         if (!(kEarly && !GF)) load_w(sb, 0, si & 1);
         if constexpr (GF) {
             half2_t nz, sc;
-            split_sz(*reinterpret_cast<const uint32_t *>(sb + kXB + L::kWB + (wave * 32 + (lane & 31)) * 4), nz, sc);
+            split_sz(*reinterpret_cast<const uint32_t *>(sb + kGOff + (wave * 32 + (lane & 31)) * 4), nz, sc);
             ec = exact_consts(nz);
-            const float *rl = reinterpret_cast<const float *>(sb + kXB + L::kWB + 1024) + wave * 32 + 4 * rq;
+            const float *rl = reinterpret_cast<const float *>(sb + kGOff + 1024) + wave * 32 + 4 * rq;
             r4[0] = *reinterpret_cast<const float4 *>(rl);
             r4[1] = *reinterpret_cast<const float4 *>(rl + 16);
         }
@@ -788,36 +825,139 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
         barrier();
     };
 
-    stage(0, 0, true);
-    stage(1, 1, TB == 8);
-    wait_one_stage(TB == 8);   // stage 0 landed (stage 1's pieces in flight)
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (grp_b) barrier();
     using GFt = std::integral_constant<bool, true>;
     using GFf = std::integral_constant<bool, false>;
-    if constexpr (TB == 16) {
-        // group = 2 k-steps, ring period 3: unroll 6 so each step's slot and group phase are static
-        for (int si = 0; si < ns; si += 6) {
-            step(0, si, GFt{});
-            step(1, si + 1, GFf{});
-            if (si + 2 < ns) {
-                step(2, si + 2, GFt{});
-                step(0, si + 3, GFf{});
+    if constexpr (RING4) {
+        // The 4-slot ring, one s_barrier per k-step.  I_kt = the span between barrier kt and barrier
+        // kt + 1.  Waves 0-3 (and, without the skew, all waves) run k-step kt in I_kt: its first half
+        // (h1: words, group constants, substeps 0, 1, half 1's A fragments) and its second half (h2:
+        // substeps 2, 3).  With the skew (MODE bit 0) waves 4-7 run h2 of k-step kt - 1, then h1 of kt:
+        // half a k-step behind their SIMD partner, B fragments and A fragments of the open k-step kept
+        // in registers across the barrier.  Every wave issues its 5 (6: group-first) pieces of stage
+        // kt + 2 into slot (kt + 2) % 4 between the MFMA quarters of the h2 it runs in I_kt.
+        //   hazard   slot / bytes                     why it holds
+        //   WAR      slot (kt + 2) % 4 held stage     its last readers (waves 4-7, h2 of kt - 2) read it in the
+        //            kt - 2                           first half of I_{kt-1} and consumed the data there: before
+        //                                             barrier kt, which every issuing wave has passed
+        //   RAW      stage kt + 1, read from I_{kt+1} each wave's counted vmcnt wait before barrier kt + 1 leaves only
+        //                                             its stage kt + 2 pieces outstanding (in-order return), so its
+        //                                             stage kt + 1 pieces are in LDS before it arrives
+        //   words    private ring slot (kt + 2) % 3   held k-step kt - 1's words, read into registers in I_{kt-1}
+        //            (this wave only)                 by this wave; stages kt, kt + 1 sit in the other two slots
+        //   epilogue the f16 image over slots 0, 1    one more barrier after waves 4-7's last h2 (ring drained)
+        // Barriers: every wave executes the same s_barrier sequence, none under a wave-dependent branch
+        // (the skew needs no paired barrier: waves 4-7 just start I_0 with h1, having issued stage 2 in a
+        // prologue burst, and run their last h2 behind the last h1).  Every wait is a literal vmcnt.  No
+        // lgkmcnt(0) in the loop: a wave's LDS reads of a slot are consumed by MFMAs at least one barrier
+        // before any wave overwrites it; the drain barrier keeps one.  No spin wait, no s_sleep.
+        auto h1 = [&](int slot, auto gf_tag) __attribute__((always_inline)) {
+            constexpr bool GF = decltype(gf_tag)::value;
+            const uint8_t *sb = smem + slot * kStage;
+            load_w(sb, 0, GF ? 0 : 1);   // the k-step's parity
+            if constexpr (GF) {
+                half2_t nz, sc;
+                split_sz(*reinterpret_cast<const uint32_t *>(sb + kGOff + (wave * 32 + (lane & 31)) * 4), nz, sc);
+                ec = exact_consts(nz);
+                const float *rl = reinterpret_cast<const float *>(sb + kGOff + 1024) + wave * 32 + 4 * rq;
+                r4[0] = *reinterpret_cast<const float4 *>(rl);
+                r4[1] = *reinterpret_cast<const float4 *>(rl + 16);
             }
-            if (si + 4 < ns) {
-                step(1, si + 4, GFt{});
-                step(2, si + 5, GFf{});
+            read_b(bA, sb, 0);
+            make_a(0, a00, a01);
+            sub(sb, bA, bB, 0, GF);
+            sub(sb, bB, bA, 1, GF);
+            make_a(1, a10, a11);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // substeps 2, 3 of the k-step in `slot`, with the pieces of stage ist into slot islot
+        auto h2 = [&](int slot, bool issue, int islot, int ist, bool igf) __attribute__((always_inline)) {
+            const uint8_t *sb = smem + slot * kStage;
+            pend_on = issue;
+            pend_slot = islot;
+            pend_st = ist;
+            pend_gf = igf;
+            sub(sb, bA, bB, 2, false);   // (substeps 2, 3 never rescale: sub's gf is unused from j = 2 on;
+            sub(sb, bB, bA, 3, false);   // igf is the ISSUED stage's group phase, not this k-step's)
+        };
+        // I_kt on slot kt % 4 (a wave-uniform run-time value: the loop is unrolled over the group
+        // period, 2 k-steps, and a slot is one s_mul away).  GF: kt opens a group, and so does
+        // kt + 2; ISSUE: stage kt + 2 exists; WAIT: a barrier ends the interval
+        auto interval = [&](auto gf_tag, int kt, auto issue_tag, auto wait_tag) __attribute__((always_inline)) {
+            constexpr bool GF = decltype(gf_tag)::value, ISSUE = decltype(issue_tag)::value,
+                           WAIT = decltype(wait_tag)::value;
+            const int slot = kt & 3, islot = (kt + 2) & 3;
+            if (grp_b && (!GF || kt > 0)) h2((kt + 3) & 3, ISSUE, islot, kt + 2, GF);   // (I_0: no open k-step yet)
+            h1(slot, gf_tag);
+            // (the last interval, the one no barrier ends: waves 4-7 go straight on to their deferred h2)
+            if (!WAIT || !grp_b) h2(slot, ISSUE, islot, kt + 2, GF);
+            if constexpr (WAIT) {
+                // stage kt + 1 landed: only this interval's pieces may be outstanding
+                if constexpr (!ISSUE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                else if constexpr (GF) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_sched_barrier(0);
             }
+            wq = wq == 2048 ? 0 : wq + 1024;
+            wq_iss = wq_iss == 2048 ? 0 : wq_iss + 1024;
+        };
+        wq_iss = 0;
+#pragma unroll
+        for (int p = 0; p < L::kPieces; ++p) piece(p, 0, 0, true);
+        wq_iss = 1024;
+#pragma unroll
+        for (int p = 0; p < L::kPieces; ++p) piece(p, 1, 1, false);
+        wq_iss = 2048;
+        // the k-steps that issue a stage (ns - 2 of them, even), then the last two
+        const int ni = ns - 2;
+        // stage 0 landed (stage 1's 5 pieces in flight).  Waves 4-7 have no h2 in I_0 to carry stage 2's
+        // pieces: they issue them here in one burst (slot 2 is fresh), 6 more in flight
+        if (grp_b && ni > 0) {
+#pragma unroll
+            for (int p = 0; p < L::kPieces; ++p) piece(p, 2, 2, true);
+            asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
         }
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        for (int kt = 0; kt < ni; kt += 2) {
+            interval(GFt{}, kt, GFt{}, GFt{});
+            interval(GFf{}, kt + 1, GFt{}, GFt{});
+        }
+        interval(GFt{}, ni, GFf{}, GFt{});
+        interval(GFf{}, ni + 1, GFf{}, GFf{});
+        barrier();   // the ring is drained: the epilogue may reuse it
     } else {
-        for (int si = 0; si < ns; si += 3) {
-            step(0, si, GFt{});
-            if (si + 1 < ns) step(1, si + 1, GFt{});
-            if (si + 2 < ns) step(2, si + 2, GFt{});
+        stage(0, 0, true);
+        stage(1, 1, TB == 8);
+        wait_one_stage(TB == 8);   // stage 0 landed (stage 1's pieces in flight)
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        if (grp_b) barrier();
+        if constexpr (TB == 16) {
+            // group = 2 k-steps, ring period 3: unroll 6 so each step's slot and group phase are static
+            for (int si = 0; si < ns; si += 6) {
+                step(0, si, GFt{});
+                step(1, si + 1, GFf{});
+                if (si + 2 < ns) {
+                    step(2, si + 2, GFt{});
+                    step(0, si + 3, GFf{});
+                }
+                if (si + 4 < ns) {
+                    step(1, si + 4, GFt{});
+                    step(2, si + 5, GFf{});
+                }
+            }
+        } else {
+            for (int si = 0; si < ns; si += 3) {
+                step(0, si, GFt{});
+                if (si + 1 < ns) step(1, si + 1, GFt{});
+                if (si + 2 < ns) step(2, si + 2, GFt{});
+            }
         }
+        if (STAG && !grp_b) barrier();
     }
-    if (STAG && !grp_b) barrier();
 
     // acc = sum_g T_g s_g / s_{G-1}: times the last group's scales, then the bias
     const int nc0 = n0 + wave * 32 + 4 * rq;   // + 16 cb: the lane's 4 columns of column block cb
@@ -887,6 +1027,14 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
     }
 }
 
+// The three schedules of the 256-token kernel (A/B: profiles/horner16_ring4/): the 3-slot ring with
+// two barriers per k-step and the stagger; the 4-slot ring (MODE bit 13) with one barrier per k-step,
+// waves in lockstep; the 4-slot ring with waves 4-7 half a k-step behind.  All three give the same bits.
+[[maybe_unused]] constexpr int kH16Ring3 = 1 | 256 | 1024;
+[[maybe_unused]] constexpr int kH16Ring4 = 256 | 1024 | 8192;
+[[maybe_unused]] constexpr int kH16Ring4Skew = 1 | 256 | 1024 | 8192;
+constexpr int kH16Arm = kH16Ring4Skew;   // the product
+
 template <int MODE, int TB = 16, int BITS = 4>
 void launch_horner16_t(const HornerGemmArgs &a, int y_f32, hipStream_t st) {
     const int nbm = (a.M + 16 * TB - 1) / (16 * TB), nbn = a.Npad / 256;
@@ -930,8 +1078,8 @@ int launch_horner_gemm(const HornerGemmArgs &a, int y_f32, hipStream_t st) {
 #if DLLM_LAB
     if (a.lab && a.bits == 4) return launch_horner_lab(a, y_f32, st);
 #endif
-    if (a.bits == 2) launch_horner16_t<1 | 256 | 1024, 16, 2>(a, y_f32, st);
-    else launch_horner16_t<1 | 256 | 1024>(a, y_f32, st);
+    if (a.bits == 2) launch_horner16_t<kH16Arm, 16, 2>(a, y_f32, st);
+    else launch_horner16_t<kH16Arm>(a, y_f32, st);
     DLLM_LAUNCH_CHECK();
     return DLLM_OK;
 }

@@ -1,7 +1,9 @@
 """A/B of the int4 g128 Horner-form GEMM schedules at M = K = N = 4096 (lab build, one process,
 interleaved rounds, HIP events): -1 = the product kernel (linear_horner.hip, staggered half
 k-steps), 25 = the same without the stagger, 24 = round 2's wq_gemm8_kernel<..., HORNER>.
-All three run the same arithmetic in the same order, so their outputs must be bit-identical."""
+All three run the same arithmetic in the same order, so their outputs must be bit-identical.
+The 256-token kernel's three schedules: 346 = 4-slot ring in lockstep, 347 = 4-slot ring with the skew
+(the product), 348 = 3-slot ring with a barrier every half k-step (profiles/horner16_ring4/)."""
 import json
 import os
 import sys
