@@ -213,11 +213,14 @@ class Calibration:
         self.min, self.max = F32(np.fmin(self.min, mn)), F32(np.fmax(self.max, mx))
         self.total_samples += x.size
         if self.max > self.min:
-            bw = F32((self.max - self.min) / F32(self.num_bins))
-            sel = x[(x >= self.min) & (x <= self.max)]
-            b = np.floor(((sel - self.min).astype(F32) / bw).astype(F32))
-            b = np.minimum(np.where(b <= 0, 0, b).astype(np.int64), self.num_bins - 1)
-            np.add.at(self.histogram, b, 1)
+            with np.errstate(all="ignore"):   # +-inf samples, max - min overflowing: inf / inf = NaN
+                bw = F32((self.max - self.min) / F32(self.num_bins))
+                sel = x[(x >= self.min) & (x <= self.max)]
+                b = np.floor(((sel - self.min).astype(F32) / bw).astype(F32))
+            # calibrate.rs:63 `as usize` saturates: NaN -> 0, negative -> 0, too large -> usize::MAX; then :64
+            # `.min(num_bins - 1)`, taken before the integer cast so nothing overflows int64.
+            b = np.where(np.isnan(b) | (b <= 0), F32(0), np.minimum(b, F32(self.num_bins - 1)))
+            np.add.at(self.histogram, np.minimum(b.astype(np.int64), self.num_bins - 1), 1)
 
     def compute_params(self, bits: int, symmetric: bool):
         if self.total_samples == 0:
@@ -263,7 +266,7 @@ class AdaptiveQuantizer:
         x = np.asarray(data, F32).ravel()
         scale, zp = self.compute_params()
         hi = int(rs_as_i32(np.array([F32(2.0 ** self.bits) - F32(1.0)], F32))[0])
-        with np.errstate(divide="ignore", invalid="ignore"):
+        with np.errstate(all="ignore"):
             t = ((x / scale).astype(F32) + zp).astype(F32)
         q = np.clip(rs_as_i32(rs_round(t)), 0, hi)
         return (q & 0xFF).astype(np.uint8), scale, zp
