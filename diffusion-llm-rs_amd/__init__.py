@@ -14,7 +14,8 @@ this package is the host-side mirror of the reference's Rust operator surface:
 * ``serde``        -- bincode / serde_json wire formats of QuantizationParams, QuantizedTensor and
   the diffusion_prefill CompressedVector hand-off record.
 * ``diffusion``    -- ``diffuse_llm``'s schedules, add_noise / p_sample (seeded device noise), the
-  phase-aware KVCacheEntry and the denoise loop (last layer fused with p_sample).
+  p_losses objective (per-sample noise MSE in a pinned summation order), the phase-aware
+  KVCacheEntry and the denoise loop (last layer fused with p_sample).
 """
 from . import _lib
 from ._lib import (CalibrationRequired, HipError, InvalidParams, QuantizationError, SerializationError,
@@ -26,7 +27,7 @@ from .quant import CalibrationData, DefaultQuantizer, QuantizationParams, Quanti
 from .kvquant import BitQuantizer, PrefillKVQuant, SystemConfig, compress_vectors, decompress_vectors
 from .linear import MixedPrecisionStack, QuantLinear
 from .diffusion import (AlphaMode, BetaSchedule, Cumprod, DenoiseLoop, DiffusionConfig, KVCacheEntry, KVCacheStore,
-                        add_noise,
+                        add_noise, noise_mse, p_losses, p_losses_coeffs,
                         p_sample, randn)
 
 __all__ = [
@@ -36,6 +37,7 @@ __all__ = [
     "QuantLinear", "MixedPrecisionStack", "QuantizationError", "InvalidParams", "UnsupportedOperation",
     "ShapeMismatch", "CalibrationRequired", "HipError", "BetaSchedule", "Cumprod", "AlphaMode", "DiffusionConfig",
     "KVCacheEntry", "KVCacheStore", "DenoiseLoop", "add_noise", "p_sample", "randn", "AdaptiveQuantizer",
+    "noise_mse", "p_losses", "p_losses_coeffs",
 ]
 
 

@@ -151,6 +151,10 @@ SIGNATURES = {
     "dllm_add_noise": (INT, [P, P, P, S, S, U64, U64, P, P, P]),
     "dllm_linear_forward_psample": (INT, [P, P, S, INT, P, P, S, INT, U64, U64, P, P, P]),
     "dllm_linear_forward_psample_ex": (INT, [P, P, S, INT, P, P, S, INT, U64, U64, P, P, P, P]),
+    "dllm_p_losses_coeffs": (INT, [P, S, P, S, P]),
+    "dllm_noise_mse_workspace": (S, [S, S]),
+    "dllm_noise_mse": (INT, [P, INT, P, S, S, U64, U64, P, P, S, P]),
+    "dllm_p_losses_host": (INT, [P, P, S, P, P, P, U64, U64, S, S, P]),
     "dllm_quantize_tensor_host": (INT, [P, S, U8, P, P, P]),
     "dllm_dequantize_tensor_host": (INT, [P, S, FL, FL, P]),
     "dllm_default_quantize_host": (INT, [P, S, INT, FL, I32, P]),

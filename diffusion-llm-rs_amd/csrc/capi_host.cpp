@@ -183,4 +183,33 @@ int dllm_linear_forward_host(dllm_linear_t h, const float *X, size_t M, float *Y
     return DLLM_OK;
 }
 
+int dllm_p_losses_host(dllm_linear_t h, const float *betas, size_t T, const float *x_start, const size_t *t,
+                       const float *noise, uint64_t seed, uint64_t offset, size_t B, size_t D, float *loss) {
+    size_t K = 0, N = 0;
+    int rc = dllm_linear_info(h, &K, &N, nullptr, nullptr);
+    if (rc) return rc;
+    if (D != K || D != N)
+        return dllm::fail(DLLM_ERR_SHAPE_MISMATCH, "Noise shape must match input shape: D must equal the model's K and N");
+    if (B && (!x_start || !loss)) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    std::vector<float> coef(2 * B);
+    if ((rc = dllm_p_losses_coeffs(betas, T, t, B, coef.data()))) return rc;
+    if (B == 0) return DLLM_OK;
+    Staging s;
+    STAGE_OK(s);
+    const float *dx = s.upload(x_start, B * D);
+    const float *dn = noise ? s.upload(noise, B * D) : nullptr;
+    const float *dc = s.upload(coef.data(), 2 * B);
+    float *dnoisy = s.alloc<float>(B * D);
+    float *deps = s.alloc<float>(B * D);
+    float *dloss = s.alloc<float>(B);
+    const size_t wsb = dllm_noise_mse_workspace(B, D);
+    void *ws = s.alloc<uint8_t>(wsb);
+    STAGE_OK(s);
+    if ((rc = dllm_add_noise(dx, dn, dc, B, D, seed, offset, dnoisy, nullptr, s.st))) return rc;
+    if ((rc = dllm_linear_forward(h, dnoisy, B, DLLM_F32, deps, DLLM_F32, s.st))) return rc;
+    if ((rc = dllm_noise_mse(deps, DLLM_F32, dn, B, D, seed, offset, dloss, ws, wsb, s.st))) return rc;
+    if ((rc = s.download(loss, dloss, B)) || (rc = s.sync())) return rc;
+    return DLLM_OK;
+}
+
 }  // extern "C"

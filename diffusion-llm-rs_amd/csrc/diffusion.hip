@@ -2,9 +2,10 @@
 // 8f rank 1): beta schedules and alpha-bar tables (host scalars, Rust f32 semantics), the
 // p_sample posterior step and the add_noise forward step (HBM-bound kernels), and the seeded
 // Gaussian noise they draw (Philox4x32-10 + a Box-Muller built only from correctly rounded
-// + - * / sqrt, so it is reproducible bit for bit on any IEEE host).
+// + - * / sqrt, so it is reproducible bit for bit on any IEEE host), and the p_losses reduction
+// (per-sample mean squared error of the predicted noise, in a summation order fixed by the header).
 //
-// Reference: diffuse-llm-rs/src/lib.rs create_beta_schedule :554-593, p_losses :615-630,
+// Reference: diffuse-llm-rs/src/lib.rs create_beta_schedule :554-593, p_losses :595-653,
 // add_noise :1100-1137, p_sample :1152-1215.
 #include "common.hpp"
 #include "diffusion_rng.hpp"
@@ -119,6 +120,138 @@ __global__ void __launch_bounds__(256) randn_kernel(uint64_t seed, uint64_t offs
 
 unsigned elem_grid(size_t n) { return grid_for((n + 3) / 4, 256, kCUs * 16); }
 
+// ---- p_losses: per-sample mean of (noise - pred)^2 in the pinned order of dllm_noise_mse ---------
+
+constexpr int kMseLanes = 256;                        // lanes of a chunk = threads of a block
+constexpr int kMseTrips = 16;                         // groups of four per lane and chunk
+constexpr size_t kMseChunk = 4 * kMseLanes * kMseTrips;   // 16384 elements
+
+inline size_t mse_chunks(size_t n) { return (n + kMseChunk - 1) / kMseChunk; }
+
+// The halving tree over the block's 256 lane sums: s[j] = s[j] + s[j + h] for j < h, h = 128 ... 1.
+// Levels 128 and 64 cross waves (through LDS); 32 ... 1 stay in wave 0, where lane j < h takes
+// exactly lane j + h's value of the level before.  The root is thread 0's return value.
+__device__ __forceinline__ float mse_tree(float s, float *lds) {
+    const int j = threadIdx.x;
+    lds[j] = s;
+    __syncthreads();
+    if (j < 128) {
+        s = s + lds[j + 128];
+        lds[j] = s;
+    }
+    __syncthreads();
+    if (j < 64) {
+        s = s + lds[j + 64];
+#pragma unroll
+        for (int h = 32; h > 0; h >>= 1) s = s + __shfl_down(s, h, 64);
+    }
+    return s;
+}
+
+__device__ __forceinline__ float4 load_pred4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ float4 load_pred4(const __half *p) {
+    const uint2 r = *reinterpret_cast<const uint2 *>(p);
+    const __half2 lo = *reinterpret_cast<const __half2 *>(&r.x), hi = *reinterpret_cast<const __half2 *>(&r.y);
+    return make_float4(__low2float(lo), __high2float(lo), __low2float(hi), __high2float(hi));
+}
+
+// s + (nz - p)^2 over the group's components 0..3, every op rounded once (-ffp-contract=off).
+__device__ __forceinline__ float mse_add4(float s, const float4 nz, const float4 p) {
+    float d = nz.x - p.x;
+    s = s + d * d;
+    d = nz.y - p.y;
+    s = s + d * d;
+    d = nz.z - p.z;
+    s = s + d * d;
+    d = nz.w - p.w;
+    return s + d * d;
+}
+
+// Block (b, c) = blockIdx.x: chunk c of sample b -> partial[b C + c], or, for a one-chunk sample,
+// whose total is that partial (the finish pass would add it to +0 only), loss[b] directly.  Groups
+// past n are +0 terms of a sum that never goes below +0: leaving them out changes no bit.
+// kStream: the noise is regenerated (noise == nullptr); an instantiation of its own, so that its
+// register budget is not the explicit form's 32 loads in flight.
+template <typename T, bool kStream>
+__global__ void __launch_bounds__(kMseLanes) noise_mse_chunk_kernel(const T *__restrict__ pred,
+                                                                    const float *__restrict__ noise, size_t n,
+                                                                    size_t C, uint64_t seed, uint64_t offset,
+                                                                    float *__restrict__ partial,
+                                                                    float *__restrict__ loss) {
+    __shared__ float lds[kMseLanes];
+    const size_t b = blockIdx.x / C, c = blockIdx.x % C;
+    const size_t base = b * n;                                        // first element of the sample
+    const size_t i0 = c * kMseChunk + 4 * static_cast<size_t>(threadIdx.x);   // this lane's group of trip 0
+    float s = 0.f;
+    if constexpr (!kStream) {
+        // HBM-bound: all 16 + 16 loads of the lane in flight before the first add
+        float4 p[kMseTrips], z[kMseTrips];
+#pragma unroll
+        for (int k = 0; k < kMseTrips; ++k) {
+            const size_t i = i0 + static_cast<size_t>(k) * (4 * kMseLanes);
+            p[k] = i < n ? load_pred4(pred + base + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+            z[k] = i < n ? *reinterpret_cast<const float4 *>(noise + base + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int k = 0; k < kMseTrips; ++k) s = mse_add4(s, z[k], p[k]);
+    } else if ((c + 1) * kMseChunk <= n) {
+        // VALU-bound, a whole chunk (block-uniform): four trips per pass with no branch between them,
+        // so four independent generator chains interleave and cover the pass's loads -- with 2-4
+        // blocks per CU there are too few waves to hide one chain's latencies otherwise (all 16 at
+        // once would take every register)
+#pragma unroll 1
+        for (int k0 = 0; k0 < kMseTrips; k0 += 4) {
+            const size_t i = i0 + static_cast<size_t>(k0) * (4 * kMseLanes);
+            float4 p[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) p[k] = load_pred4(pred + base + i + static_cast<size_t>(k) * (4 * kMseLanes));
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float z[4];
+                rng::normal4(seed, (offset + base + i) / 4 + static_cast<size_t>(k) * kMseLanes, z);
+                s = mse_add4(s, make_float4(z[0], z[1], z[2], z[3]), p[k]);
+            }
+        }
+    } else {
+        for (int k = 0; k < kMseTrips; ++k) {
+            const size_t i = i0 + static_cast<size_t>(k) * (4 * kMseLanes);
+            if (i < n) {
+                const float4 p = load_pred4(pred + base + i);
+                float z[4];
+                rng::normal4(seed, (offset + base + i) / 4, z);
+                s = mse_add4(s, make_float4(z[0], z[1], z[2], z[3]), p);
+            }
+        }
+    }
+    s = mse_tree(s, lds);
+    if (threadIdx.x == 0) {
+        if (C == 1)
+            loss[b] = s / static_cast<float>(n);
+        else
+            partial[blockIdx.x] = s;
+    }
+}
+
+template <typename T>
+void launch_mse_chunks(const T *pred, const float *noise, size_t n, size_t C, uint64_t seed, uint64_t offset,
+                       float *partial, float *loss, unsigned grid, hipStream_t st) {
+    if (noise)
+        noise_mse_chunk_kernel<T, false><<<grid, kMseLanes, 0, st>>>(pred, noise, n, C, seed, offset, partial, loss);
+    else
+        noise_mse_chunk_kernel<T, true><<<grid, kMseLanes, 0, st>>>(pred, noise, n, C, seed, offset, partial, loss);
+}
+
+// Block b: the sample's C partials to 256 lanes round-robin, the same tree, the division.
+__global__ void __launch_bounds__(kMseLanes) noise_mse_finish_kernel(const float *__restrict__ partial, size_t n,
+                                                                     size_t C, float *__restrict__ loss) {
+    __shared__ float lds[kMseLanes];
+    const float *P = partial + blockIdx.x * C;
+    float s = 0.f;
+    for (size_t c = threadIdx.x; c < C; c += kMseLanes) s = s + P[c];
+    s = mse_tree(s, lds);
+    if (threadIdx.x == 0) loss[blockIdx.x] = s / static_cast<float>(n);
+}
+
 }  // namespace
 }  // namespace dllm
 
@@ -204,6 +337,47 @@ int dllm_add_noise_coeffs(const float *betas, size_t T, int cumprod, const size_
         const size_t ti = std::min(t[i], T - 1);
         coef[2 * i + 0] = std::sqrt(ab[ti]);
         coef[2 * i + 1] = std::sqrt(1.0f - ab[ti]);
+    }
+    return DLLM_OK;
+}
+
+int dllm_p_losses_coeffs(const float *betas, size_t T, const size_t *t, size_t B, float *coef) {
+    if (T == 0) return fail(DLLM_ERR_INVALID_PARAMS, "empty schedule");
+    if (!betas || (B && (!t || !coef))) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    for (size_t i = 0; i < B; ++i)   // alpha_bars[t] panics (lib.rs:645): no clamp here
+        if (t[i] >= T) return fail(DLLM_ERR_INVALID_PARAMS, "timestep out of range of the schedule (lib.rs:645)");
+    return dllm_add_noise_coeffs(betas, T, DLLM_ABAR_INCLUSIVE, t, B, coef);
+}
+
+size_t dllm_noise_mse_workspace(size_t B, size_t n) { return B * mse_chunks(n) * sizeof(float); }
+
+int dllm_noise_mse(const void *pred, int pred_dtype, const float *noise, size_t B, size_t n, uint64_t seed,
+                   uint64_t offset, float *loss, void *workspace, size_t workspace_bytes, dllm_stream_t stream) {
+    if (pred_dtype != DLLM_F32 && pred_dtype != DLLM_F16)
+        return fail(DLLM_ERR_UNSUPPORTED, "pred_dtype must be DLLM_F32 or DLLM_F16");
+    if (B == 0) return DLLM_OK;
+    if (n == 0) return fail(DLLM_ERR_INVALID_PARAMS, "the mean over an empty sample is undefined");
+    if (n % 4) return fail(DLLM_ERR_UNSUPPORTED, "n must be a multiple of 4");
+    if (!noise && offset % 4) return fail(DLLM_ERR_INVALID_PARAMS, "offset must be a multiple of 4");
+    if (!pred || !loss || !workspace) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    if ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(loss) |
+         reinterpret_cast<uintptr_t>(workspace)) % 16)
+        return fail(DLLM_ERR_INVALID_PARAMS, "pred, noise, loss and workspace must be 16-byte aligned");
+    if (workspace_bytes < dllm_noise_mse_workspace(B, n))
+        return fail(DLLM_ERR_INVALID_PARAMS, "workspace smaller than dllm_noise_mse_workspace(B, n)");
+    const size_t C = mse_chunks(n);
+    if (C > 0x7fffffffu / B) return fail(DLLM_ERR_UNSUPPORTED, "B * ceil(n / 16384) exceeds the grid limit");
+    const unsigned grid = static_cast<unsigned>(B * C);
+    float *partial = static_cast<float *>(workspace);
+    hipStream_t st = as_stream(stream);
+    if (pred_dtype == DLLM_F16)
+        launch_mse_chunks(static_cast<const __half *>(pred), noise, n, C, seed, offset, partial, loss, grid, st);
+    else
+        launch_mse_chunks(static_cast<const float *>(pred), noise, n, C, seed, offset, partial, loss, grid, st);
+    DLLM_LAUNCH_CHECK();
+    if (C > 1) {
+        noise_mse_finish_kernel<<<static_cast<unsigned>(B), kMseLanes, 0, st>>>(partial, n, C, loss);
+        DLLM_LAUNCH_CHECK();
     }
     return DLLM_OK;
 }

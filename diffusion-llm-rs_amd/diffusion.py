@@ -4,6 +4,7 @@ config C5), mirroring ``diffuse_llm_rs::diffuse_llm`` (diffuse-llm-rs/src/lib.rs
 * ``DiffusionConfig.create_beta_schedule``  -- lib.rs:554-593 (host scalars, Rust f32 semantics)
 * ``add_noise``                             -- DiffuseLLM::add_noise, lib.rs:1100-1137
 * ``p_sample``                              -- DiffuseLLM::p_sample, lib.rs:1152-1215
+* ``p_losses`` / ``noise_mse``              -- DiffuseLLM::p_losses, lib.rs:615-653
 * ``KVCacheEntry``                          -- phase-aware dual-precision KV cache, lib.rs:121-313
 * ``DenoiseLoop``                           -- DiffuseLLM::sample, lib.rs:853-955, with an
   L-layer quantized denoiser whose last layer runs p_sample in its GEMM epilogue.
@@ -161,6 +162,106 @@ def p_sample(config: DiffusionConfig, x_t: torch.Tensor, t, noise_pred: torch.Te
     check(_lib.load().dllm_p_sample(_ptr(x), _ptr(eps), None if nz is None else _ptr(nz), _ptr(coef), B, D, int(flag),
                                     seed, offset, _ptr(out), _stream()))
     return out
+
+
+def p_losses_coeffs(config: DiffusionConfig, t, B: int) -> np.ndarray:
+    """p_losses scalars (lib.rs:627-630, :645-649): host f32 [B, 2] = {sqrt(abar_t), sqrt(1 - abar_t)}
+    of the inclusive scan.  Unlike ``add_noise_coeffs`` no clamp: t >= num_timesteps raises
+    InvalidParams (``alpha_bars[t]`` panics in the reference); a ``t`` of the wrong length too."""
+    betas = config.create_beta_schedule()
+    tt = np.asarray([t] * B if np.isscalar(t) else t, dtype=np.uint64)
+    if tt.ndim != 1 or tt.size != B:
+        raise _lib.InvalidParams("Timesteps must match batch size")   # lib.rs:636
+    coef = np.zeros((B, 2), np.float32)
+    check(_lib.load().dllm_p_losses_coeffs(_ptr(betas), betas.size, _ptr(tt), B, _ptr(coef)))
+    return coef
+
+
+_mse_ws = {}   # (device index, stream) -> grow-only u8 workspace of noise_mse
+
+
+def _mse_workspace(device, nbytes):
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _mse_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _mse_ws[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def noise_mse(pred: torch.Tensor, noise: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0,
+              samples: Optional[int] = None) -> torch.Tensor:
+    """Per-sample mean of (noise - pred)^2 (dllm_noise_mse; the summation order is pinned in
+    include/dllm_quant.h, so the bits depend on the data alone) -> f32 [B] on the device.
+
+    ``pred`` f32 or f16: [B, n], or [M, N] with ``samples`` = B and M % B == 0 (each sample M / B
+    consecutive rows).  ``noise``: f32 of pred's shape, or None for stream elements offset .. of
+    ``seed`` -- the ones ``add_noise`` drew with the same seed and offset -- regenerated in the kernel."""
+    if pred.dim() != 2:
+        raise _lib.ShapeMismatch("pred must be [B, n] or [M, N]")
+    if not pred.is_cuda or not pred.is_contiguous() or pred.dtype not in (torch.float16, torch.float32):
+        pred = pred.to(device="cuda", dtype=torch.float16 if pred.dtype == torch.float16 else torch.float32).contiguous()
+    B = int(pred.shape[0]) if samples is None else int(samples)
+    if B <= 0 or pred.shape[0] % B:
+        raise _lib.ShapeMismatch(f"{pred.shape[0]} rows do not split into {B} samples")
+    n = pred.numel() // B
+    nz = None
+    if noise is not None:
+        if tuple(noise.shape) != tuple(pred.shape):
+            raise _lib.ShapeMismatch("Noise shape must match input shape")   # lib.rs:640
+        nz = noise.to(device=pred.device, dtype=torch.float32).contiguous()
+    L = _lib.load()
+    loss = torch.empty(B, dtype=torch.float32, device=pred.device)
+    ws = _mse_workspace(pred.device, L.dllm_noise_mse_workspace(B, n))
+    check(L.dllm_noise_mse(_ptr(pred), _lib.F16 if pred.dtype == torch.float16 else _lib.F32,
+                           None if nz is None else _ptr(nz), B, n, int(seed), int(offset), _ptr(loss), _ptr(ws),
+                           ws.numel(), _stream()))
+    return loss
+
+
+def _run_model(model, x: torch.Tensor) -> torch.Tensor:
+    """eps = model(x): a callable, or layers chained as DenoiseLoop.step chains them (f16 between
+    layers, f32 out of the last)."""
+    if callable(model):
+        return model(x)
+    layers = list(model)
+    h = x
+    for layer in layers[:-1]:
+        h = layer(h, out_dtype=torch.float16)
+    return layers[-1](h, out_dtype=torch.float32)
+
+
+def p_losses(config: DiffusionConfig, model, x_start: torch.Tensor, t, noise: Optional[torch.Tensor] = None,
+             seed: int = 0, offset: int = 0):
+    """DiffuseLLM::p_losses (lib.rs:615-653): (loss f32 [B], noisy, noise).
+
+    ``x_start`` [B, D], or [B, R, d] token-major (sample b = rows b R .. of the [B R, d] matrix the
+    model sees).  noisy = x_start sqrt(abar_t) + noise sqrt(1 - abar_t) with the inclusive scan
+    (= ``add_noise(..., cumprod=Cumprod.INCLUSIVE)`` for t < num_timesteps), eps = model(noisy) --
+    ``model`` a callable x -> eps (f32 or f16) or a sequence of layers chained as DenoiseLoop.step chains them --
+    and loss[b] = mean (noise - eps)^2 over sample b (``noise_mse``).  The reference text breaks off
+    after the model call (:652); the loss is its doc comment's "mean squared error between the
+    predicted and actual noise ... for each sample in the batch".  With ``noise`` None the noise is
+    stream elements offset .. of ``seed``, drawn in add_noise and again in the loss kernel and never
+    stored: the returned noise is then None."""
+    x0 = _dev32(x_start)
+    if x0.dim() not in (2, 3):
+        raise _lib.ShapeMismatch("x_start must be [B, D] or [B, R, d]")
+    B = int(x0.shape[0])
+    coef = torch.from_numpy(p_losses_coeffs(config, t, B)).to(x0.device)
+    nz = None
+    if noise is not None:
+        if tuple(noise.shape) != tuple(x0.shape):
+            raise _lib.ShapeMismatch("Noise shape must match input shape")   # lib.rs:640
+        nz = _dev32(noise)
+    D = x0.numel() // B if B else 0
+    noisy = torch.empty_like(x0)
+    check(_lib.load().dllm_add_noise(_ptr(x0), None if nz is None else _ptr(nz), _ptr(coef), B, D, int(seed),
+                                     int(offset), _ptr(noisy), None, _stream()))
+    eps = _run_model(model, noisy.reshape(-1, x0.shape[-1]))
+    if eps.numel() != x0.numel():
+        raise _lib.ShapeMismatch("Noise shape must match input shape")   # the prediction's, lib.rs:640
+    loss = noise_mse(eps.reshape(B, D), None if nz is None else nz.reshape(B, D), seed, offset)
+    return loss, noisy, nz
 
 
 class KVCacheEntry:
@@ -505,6 +606,13 @@ class DenoiseLoop:
             eps = last(h, out_dtype=torch.float32)
             self.ops.p_sample(x, eps, noise, coef, flag, self.seed, offset, out)
         return out
+
+    def p_losses(self, x_start: torch.Tensor, t, noise: Optional[torch.Tensor] = None, offset: int = 0):
+        """DiffuseLLM::p_losses (lib.rs:615-653) on the loop's own layers, seed and config:
+        ``p_losses(self.config, self.layers, x_start, t, noise, self.seed, offset)`` ->
+        (loss f32 [B], noisy, noise).  Always the inclusive alpha-bar scan, as p_losses has it in the
+        reference (:627-630), whatever ``cumprod`` the loop samples with."""
+        return p_losses(self.config, self.layers, x_start, t, noise=noise, seed=self.seed, offset=offset)
 
     def kv_step(self, t: int, num_steps: int):
         """lib.rs:880-916: phase switch, progressive decode bits, update (re-quantize), dequant."""

@@ -459,6 +459,44 @@ int dllm_linear_forward_psample_ex(dllm_linear_t h, const void *X, size_t M, int
                                    uint64_t offset, const float *noise, float *x_prev, void *x_prev_f16,
                                    dllm_stream_t stream);
 
+/* ---- 8f rank 1, p_losses: the noise-prediction loss (DiffuseLLM::p_losses, lib.rs:595-653) ------
+ * noisy = x_start sqrt(abar_t) + noise sqrt(1 - abar_t) with the INCLUSIVE scan (:627-630, :645-649),
+ * eps = model(noisy), loss[b] = mean_i (noise - eps)^2 over sample b.  The reference text stops at
+ * `model.forward(&noisy, t)` (:652); the loss is its doc comment's ("the mean squared error between
+ * the predicted and actual noise", "the loss value for each sample in the batch", Array1<f32>): a
+ * build-defined completion, in an order the reference could not pin either.
+ *
+ * Summation order (the contract: the bits depend on nothing else -- not the grid, the wave
+ * scheduling or the device).  Sample b has n = rows_per_sample N contiguous elements; pred is f32,
+ * or f16 widened exactly.  d_i = RN(noise_i - pred_i), e_i = RN(d_i d_i); no fused multiply-add.
+ *   Chunk c = elements [16384 c, 16384 (c + 1)) of the sample; elements at index >= n count as +0.
+ *   Groups of four go to 256 lanes round-robin (group g = chunk elements 4g .. 4g + 3, lane g mod
+ *   256).  Lane j adds its groups in increasing g, components 0, 1, 2, 3, from +0 (at most 64
+ *   adds).  The lanes combine by the halving tree s[j] = s[j] + s[j + h] for j < h, h = 128, 64,
+ *   ..., 1; s[0] is the chunk partial P[b][c].
+ *   The C = ceil(n / 16384) partials go to 256 lanes round-robin (P[c] to lane c mod 256,
+ *   increasing c, from +0); the same tree combines them; loss[b] = RN(total / (float)n).
+ * Every term is >= +0, so for finite inputs whose squares do not overflow the relative error
+ * against the exact mean is <= 85 * 2^-24 ~ 5.1e-6 (2 roundings per element, <= 64 adds + 8 tree
+ * levels per chunk, <= ceil(C / 256) adds + 8 levels over the partials, 1 division). */
+/* p_losses scalars: coef[B][2] = {sqrt(abar_t), sqrt(1 - abar_t)} of the inclusive scan; for t < T
+ * the bits of dllm_add_noise_coeffs(..., DLLM_ABAR_INCLUSIVE, ...).  No clamp: `alpha_bars[t]`
+ * panics in the reference for t >= T, so t[i] >= T -> DLLM_ERR_INVALID_PARAMS.  Host arrays. */
+int dllm_p_losses_coeffs(const float *betas, size_t T, const size_t *t, size_t B, float *coef);
+/* Bytes of device workspace dllm_noise_mse needs (the chunk partials): B * ceil(n / 16384) * 4. */
+size_t dllm_noise_mse_workspace(size_t B, size_t n);
+/* loss[b] (device f32 [B]) = mean over sample b's n elements of (noise - pred)^2 in the order
+ * above.  pred: device [B][n], pred_dtype DLLM_F32 or DLLM_F16 (anything else -> UNSUPPORTED).
+ * noise: device f32 [B][n], or NULL = stream element offset + b n + i of `seed` regenerated in the
+ * kernel -- the elements dllm_add_noise drew for the same seed and offset, never stored (offset %
+ * 4 != 0 -> INVALID_PARAMS).  n % 4 != 0 -> UNSUPPORTED; n == 0 with B > 0 -> INVALID_PARAMS; B == 0
+ * -> DLLM_OK, nothing written.  pred, loss and workspace non-NULL; they and noise 16-byte aligned;
+ * workspace_bytes >= dllm_noise_mse_workspace(B, n); else INVALID_PARAMS and nothing is launched.
+ * A NaN or inf in a sample makes that sample's loss NaN or inf and touches no other sample.
+ * Asynchronous on `stream`; never synchronises or allocates (graph-capturable from the first call). */
+int dllm_noise_mse(const void *pred, int pred_dtype, const float *noise, size_t B, size_t n, uint64_t seed,
+                   uint64_t offset, float *loss, void *workspace, size_t workspace_bytes, dllm_stream_t stream);
+
 /* ---- host-slice variants (synchronous; stage through device memory; not graph-capturable) ----
  * The literal shapes of the reference's Rust signatures, for callers holding host slices. */
 /* quantize_tensor(&[f32], u8) -> (Vec<u8>, f32, f32): codes one per byte (quantization.rs:38-68). */
@@ -477,6 +515,13 @@ int dllm_compress_vector_host(const float *x, size_t n, uint8_t bits, uint8_t *o
 int dllm_linear_create_host(const float *W, const float *bias, size_t K, size_t N, uint8_t bits, size_t group,
                             dllm_linear_t *out);
 int dllm_linear_forward_host(dllm_linear_t h, const float *X, size_t M, float *Y);
+/* DiffuseLLM::p_losses (lib.rs:615-653) with SimpleDiffusionModel as the linear handle: x_start
+ * [B][D], t[B], noise [B][D] or NULL (= the seeded stream from `offset`), loss[B]; all host.
+ * D must equal the handle's K and N ("Noise shape must match input shape", :640), else
+ * DLLM_ERR_SHAPE_MISMATCH.  dllm_add_noise with dllm_p_losses_coeffs, dllm_linear_forward (f32
+ * out), dllm_noise_mse. */
+int dllm_p_losses_host(dllm_linear_t model, const float *betas, size_t T, const float *x_start, const size_t *t,
+                       const float *noise, uint64_t seed, uint64_t offset, size_t B, size_t D, float *loss);
 
 #ifdef __cplusplus
 }
