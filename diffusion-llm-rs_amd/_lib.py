@@ -142,6 +142,7 @@ SIGNATURES = {
     "dllm_linear_destroy": (INT, [P]),
     "dllm_kv_attention": (INT, [P, P, P, P, P, U8, S, S, S, P, P]),
     "dllm_kv_attention_ex": (INT, [P, S, P, P, P, P, U8, S, S, S, P, P]),
+    "dllm_kv_attention_hd": (INT, [P, S, P, P, P, P, U8, S, S, S, P, P]),
     "dllm_beta_schedule": (INT, [INT, S, FL, FL, P]),
     "dllm_alpha_bars": (INT, [P, S, INT, P, P]),
     "dllm_p_sample_coeffs": (INT, [P, S, INT, INT, P, S, P, P]),

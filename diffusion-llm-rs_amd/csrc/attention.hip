@@ -10,7 +10,8 @@
 // exponent and the final normalisation: fewer roundings than dequantizing to f16 first.
 //
 // Layout: Q, O f16 [Sq][H][D]; K, V codes of any width 1..8 in the canonical packed bitstream of the
-// flattened [Skv][H][D] tensor (one per-tensor {scale, zp} pair each, on the device), D = 128; or
+// flattened [Skv][H][D] tensor (one per-tensor {scale, zp} pair each, on the device), D = 64 or 128
+// (one instantiation each; the figures in these comments are D = 128's unless they say otherwise); or
 // K, V f32 (the cache's width-0 state), staged as f16 x 2^-e with the scale 2^e (kv_stage_f32_kernel).
 // Workgroup = 8 waves = 256 queries of one head; every 64-key block of K and V is staged once in
 // LDS (K as [key][d], V transposed as [d][key]) and shared by the 8 waves.
@@ -65,31 +66,54 @@ __device__ __forceinline__ float16_t attn_mf16_abl(const half8_t &a, const half8
 namespace dllm {
 namespace {
 
-constexpr int kD = 128;          // head dim
 constexpr int kKB = 64;          // keys per block
 constexpr int kWaves = 8;
 constexpr int kQT = 32 * kWaves; // queries per workgroup
-constexpr int kKRow = kD + 8;    // K row stride (halves): 272 B, conflict-free b128 fragment reads
 constexpr int kVRow = kKB + 8;   // Vt row stride (halves): 144 B
 
-template <int NB>
-struct AttnSmemN {
-    _Float16 k[NB][kKB][kKRow];   // NB x 17 KiB
-    _Float16 vt[NB][kD][kVRow];   // NB x 18 KiB
-    float bcast[kWaves][32];      // per-wave per-query factors (alpha, then 1/l)
-};
-using AttnSmem = AttnSmemN<2>;
-
+// The geometry of a head dim D (the product instantiates 64 and 128).
 // Workspace image of one (head, key block): the K tile then the transposed V tile, byte for byte
 // the LDS layout (row padding included), so one 1-KiB LDS-DMA piece per wave-instruction moves it.
-constexpr int kKImg = kKB * kKRow * 2;          // 17408 B = 17 pieces
-constexpr int kVImg = kD * kVRow * 2;           // 18432 B = 18 pieces
-constexpr int kImg = kKImg + kVImg;
-static_assert(kKImg % 1024 == 0 && kVImg % 1024 == 0, "images must be whole 1-KiB DMA pieces");
+template <int D>
+struct AttnGeo {
+    static_assert(D == 64 || D == 128, "head dim 64 or 128");
+    // K row stride (halves): 272 B at D = 128, 144 B (the V image's stride) at 64: conflict-free
+    // b128 fragment reads
+    static constexpr int kKRow = D + 8;
+    static constexpr int kKImg = kKB * kKRow * 2;   // D = 128: 17408 B = 17 pieces; 64: 9216 B = 9
+    static constexpr int kVImg = D * kVRow * 2;     // D = 128: 18432 B = 18 pieces; 64: 9216 B = 9
+    static constexpr int kImg = kKImg + kVImg;      // 35 KiB; 18 KiB
+    static_assert(kKImg % 1024 == 0 && kVImg % 1024 == 0, "images must be whole 1-KiB DMA pieces");
+};
 
-// Codes of one thread's share of a block, loaded to registers ahead of the MFMAs.
-// K: thread t < 256 owns key t>>2, dims 32*(t&3) .. +32 (one row chunk).
-// V: thread t >= 256 owns keys 4*((t-256)>>4) .. +4, dims 8*((t-256)&15) .. +8 (a 4x8 micro-tile).
+template <int D, int NB>
+struct AttnSmemD {
+    _Float16 k[NB][kKB][AttnGeo<D>::kKRow];   // D = 128: NB x 17 KiB; 64: NB x 9 KiB
+    _Float16 vt[NB][D][kVRow];                // D = 128: NB x 18 KiB; 64: NB x 9 KiB
+    float bcast[kWaves][32];                  // per-wave per-query factors (alpha, then 1/l)
+};
+
+#if DLLM_LAB   // the lab kernels (lab/attn*.inc) are D = 128 only and name its geometry directly
+constexpr int kD = 128;
+constexpr int kKRow = AttnGeo<kD>::kKRow, kKImg = AttnGeo<kD>::kKImg, kVImg = AttnGeo<kD>::kVImg, kImg = AttnGeo<kD>::kImg;
+template <int NB> using AttnSmemN = AttnSmemD<kD, NB>;
+using AttnSmem = AttnSmemN<2>;
+#endif
+
+// Codes of one thread's share of a block, loaded to registers ahead of the MFMAs.  The shares are
+// the same for every D; a row takes D / 32 K threads and a 4-key group D / 8 V threads, and the
+// threads past those (D = 64: t in 128..255 and 384..511) own nothing (kv_has_share: the callers'
+// guard; the share functions below assume it).
+// K: thread t < 256 owns key t / (D/32), dims 32*(t % (D/32)) .. +32 (one row chunk).
+// V: thread t >= 256 owns keys 4*((t-256) / (D/8)) .. +4, dims 8*((t-256) % (D/8)) .. +8 (a 4x8 micro-tile).
+template <int D> constexpr int kKThr = D / 32;   // K threads per key
+template <int D> constexpr int kVThr = D / 8;    // V threads per 4-key group
+template <int D>
+__device__ __forceinline__ bool kv_has_share(int tid) {
+    static_assert(kKB * kKThr<D> == kKB / 4 * kVThr<D> && kKB * kKThr<D> <= 256, "as many K threads as V threads");
+    if constexpr (kKB * kKThr<D> == 256) return true;
+    else return (tid & 255) < kKB * kKThr<D>;
+}
 template <int BITS>
 struct Raw {
     uint32_t w[BITS == 4 ? 4 : 8];
@@ -99,12 +123,12 @@ template <int BITS> constexpr int kVWords = (8 * BITS + 31) / 32;
 
 // 32-bit byte offsets through buffer resources: keys at or past S read as 0 (out of range, no
 // memory access) instead of being clamped, and no 64-bit address math per block.
-template <int BITS>
+template <int BITS, int D>
 __device__ __forceinline__ void load_raw(Raw<BITS> &r, __amdgpu_buffer_rsrc_t krs, __amdgpu_buffer_rsrc_t vrs,
                                          int tid, int jk, int jv, int H, int h) {
-    constexpr int kRowB = kD * BITS / 8;   // packed bytes per (key, head) row
+    constexpr int kRowB = D * BITS / 8;   // packed bytes per (key, head) row
     if (tid < 256) {
-        const int key = tid >> 2, d0 = 32 * (tid & 3);
+        const int key = tid / kKThr<D>, d0 = 32 * (tid % kKThr<D>);
         const uint32_t off = static_cast<uint32_t>(((jk + key) * H + h) * kRowB + d0 * BITS / 8);
         if constexpr (BITS == 4) {
             const uint4 v = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, 0, 0));
@@ -115,7 +139,7 @@ __device__ __forceinline__ void load_raw(Raw<BITS> &r, __amdgpu_buffer_rsrc_t kr
             r.w[0] = a.x; r.w[1] = a.y; r.w[2] = a.z; r.w[3] = a.w; r.w[4] = b.x; r.w[5] = b.y; r.w[6] = b.z; r.w[7] = b.w;
         }
     } else {
-        const int t = tid - 256, k4 = 4 * (t >> 4), d0 = 8 * (t & 15);
+        const int t = tid - 256, k4 = 4 * (t / kVThr<D>), d0 = 8 * (t % kVThr<D>);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint32_t off = static_cast<uint32_t>(((jv + k4 + i) * H + h) * kRowB + d0 * BITS / 8);
@@ -157,8 +181,8 @@ __device__ __forceinline__ half2_t pair_qz(const uint32_t (&w)[N], int w0, int i
 __host__ __device__ constexpr int kv_pos16(int k) { return 8 * ((k >> 2) & 3) + 4 * ((k >> 4) & 1) + (k & 3); }
 
 // The thread's unpacked share into the LDS tiles.  K: the 32 codes of w[0 ..] to bk[key][d0 .. d0 + 32).
-template <int BITS, int N>
-__device__ __forceinline__ void put_k(const uint32_t (&w)[N], _Float16 (&bk)[kKB][kKRow], int key, int d0, half2_t kz) {
+template <int BITS, int N, int KROW>
+__device__ __forceinline__ void put_k(const uint32_t (&w)[N], _Float16 (&bk)[kKB][KROW], int key, int d0, half2_t kz) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {   // 4 x 8 codes -> 4 x b128 stores
         half8_t out;
@@ -174,8 +198,8 @@ __device__ __forceinline__ void put_k(const uint32_t (&w)[N], _Float16 (&bk)[kKB
 }
 // V: keys k4 .. k4 + 3, the 8 codes of key i in w[kVWords<BITS> i ..], to bvt[d0 .. d0 + 8)[key position].
 // VL16: the V image in kv_pos16 order (kv_attention16_kernel); else kv_pos (kv_attention5_kernel).
-template <int BITS, bool VL16, int N>
-__device__ __forceinline__ void put_v(const uint32_t (&w)[N], _Float16 (&bvt)[kD][kVRow], int k4, int d0, half2_t vz) {
+template <int BITS, bool VL16, int N, int D>
+__device__ __forceinline__ void put_v(const uint32_t (&w)[N], _Float16 (&bvt)[D][kVRow], int k4, int d0, half2_t vz) {
     _Float16 v[4][8];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -194,45 +218,46 @@ __device__ __forceinline__ void put_v(const uint32_t (&w)[N], _Float16 (&bvt)[kD
         *reinterpret_cast<half4_t *>(&bvt[d0 + dd][kp4]) = half4_t{v[0][dd], v[1][dd], v[2][dd], v[3][dd]};
 }
 
-template <int BITS, bool VL16 = false>
-__device__ __forceinline__ void store_raw(const Raw<BITS> &r, _Float16 (&bk)[kKB][kKRow], _Float16 (&bvt)[kD][kVRow],
+template <int BITS, bool VL16 = false, int D>
+__device__ __forceinline__ void store_raw(const Raw<BITS> &r, _Float16 (&bk)[kKB][AttnGeo<D>::kKRow], _Float16 (&bvt)[D][kVRow],
                                           int tid, half2_t kz, half2_t vz) {
     if (tid < 256) {
-        put_k<BITS>(r.w, bk, tid >> 2, 32 * (tid & 3), kz);
+        put_k<BITS>(r.w, bk, tid / kKThr<D>, 32 * (tid % kKThr<D>), kz);
     } else {
         const int t = tid - 256;
-        put_v<BITS, VL16>(r.w, bvt, 4 * (t >> 4), 8 * (t & 15), vz);
+        put_v<BITS, VL16>(r.w, bvt, 4 * (t / kVThr<D>), 8 * (t % kVThr<D>), vz);
     }
 }
 
 // The widths without a power-of-two code (1, 2, 3, 5, 6, 7): the same thread ownership and tiles,
-// loaded and unpacked per branch.  A (key, head) row is 16 BITS bytes, so the K thread's 32 codes
-// are BITS whole dwords; the V thread's 8 codes of a key are BITS bytes at a byte offset that is
+// loaded and unpacked per branch.  A (key, head) row is D BITS / 8 bytes (16 BITS, or 8 BITS at
+// D = 64: whole dwords either way) and the K thread's 32 codes are BITS whole dwords of it; the V
+// thread's 8 codes of a key are BITS bytes at a byte offset that is
 // not dword-aligned for odd BITS: it loads the covering aligned dwords and funnel-shifts them down
 // to bit 0.  Every load stays a range-checked buffer load (a key at or past S reads 0 with no
 // memory access); a covering dword that the shift does not need may lie past the row or the
 // tensor: its bits are shifted out.
-template <int BITS>
-__device__ __forceinline__ void stage_gen(__amdgpu_buffer_rsrc_t krs, __amdgpu_buffer_rsrc_t vrs, _Float16 (&bk)[kKB][kKRow],
-                                          _Float16 (&bvt)[kD][kVRow], int tid, int j0, int H, int h, half2_t kz,
-                                          half2_t vz) {
-    constexpr uint32_t kRowB = kD * BITS / 8;
+template <int BITS, int D>
+__device__ __forceinline__ void stage_gen(__amdgpu_buffer_rsrc_t krs, __amdgpu_buffer_rsrc_t vrs,
+                                          _Float16 (&bk)[kKB][AttnGeo<D>::kKRow], _Float16 (&bvt)[D][kVRow], int tid,
+                                          int j0, int H, int h, half2_t kz, half2_t vz) {
+    constexpr uint32_t kRowB = D * BITS / 8;
     if (tid < 256) {
-        const int key = tid >> 2, d0 = 32 * (tid & 3);
-        const uint32_t off = (static_cast<uint32_t>(j0 + key) * H + h) * kRowB + (tid & 3) * 4 * BITS;
+        const int key = tid / kKThr<D>, d0 = 32 * (tid % kKThr<D>);
+        const uint32_t off = (static_cast<uint32_t>(j0 + key) * H + h) * kRowB + (tid % kKThr<D>) * 4 * BITS;
         uint32_t w[BITS + 1];
 #pragma unroll
         for (int j = 0; j < BITS; ++j) w[j] = __builtin_amdgcn_raw_buffer_load_b32(krs, off + 4 * j, 0, 0);
         w[BITS] = 0;
         put_k<BITS>(w, bk, key, d0, kz);
     } else {
-        const int t = tid - 256, k4 = 4 * (t >> 4), d0 = 8 * (t & 15);
+        const int t = tid - 256, k4 = 4 * (t / kVThr<D>), d0 = 8 * (t % kVThr<D>);
         constexpr int kSMax = (BITS & 1) ? 24 : (BITS & 2) ? 16 : 0;   // largest shift
         constexpr int NW = (kSMax + 8 * BITS + 31) / 32, NN = kVWords<BITS>;
         uint32_t w[4 * NN + 1];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const uint32_t off = (static_cast<uint32_t>(j0 + k4 + i) * H + h) * kRowB + (t & 15) * BITS;
+            const uint32_t off = (static_cast<uint32_t>(j0 + k4 + i) * H + h) * kRowB + (t % kVThr<D>) * BITS;
             const uint32_t a = off & ~3u, sh = 8 * (off & 3u);
             uint32_t raw[NW + 1];
 #pragma unroll
@@ -249,32 +274,35 @@ __device__ __forceinline__ void stage_gen(__amdgpu_buffer_rsrc_t krs, __amdgpu_b
 // Pre-pass: unpack block kb of head h to its LDS image (through LDS, so the stores to the
 // workspace are coalesced 16-B rows).  Keys past S read as code 0 (buffer range check); the
 // attention kernel masks their scores and their P is 0.
-template <int BITS, bool VL16 = false>
+template <int BITS, bool VL16 = false, int D = 128>
 __global__ void __launch_bounds__(512) kv_stage_kernel(const uint8_t *__restrict__ Kq, const float *__restrict__ kp,
                                                       const uint8_t *__restrict__ Vq, const float *__restrict__ vp,
                                                       int S, int H, int nkb, uint8_t *__restrict__ img) {
-    __shared__ __attribute__((aligned(16))) _Float16 tk[kKB][kKRow];
-    __shared__ __attribute__((aligned(16))) _Float16 tv[kD][kVRow];
+    using G = AttnGeo<D>;
+    __shared__ __attribute__((aligned(16))) _Float16 tk[kKB][G::kKRow];
+    __shared__ __attribute__((aligned(16))) _Float16 tv[D][kVRow];
     const int tid = threadIdx.x, kb = blockIdx.x, h = blockIdx.y;
     const _Float16 nkz = static_cast<_Float16>(-(1024.0f + kp[1]));
     const _Float16 nvz = static_cast<_Float16>(-(1024.0f + vp[1]));
     const half2_t kz{nkz, nkz}, vz{nvz, nvz};
-    const int nbytes = static_cast<int>(static_cast<size_t>(S) * H * kD * BITS / 8);
+    const int nbytes = static_cast<int>(static_cast<size_t>(S) * H * D * BITS / 8);
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(Kq), 0, nbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(Vq), 0, nbytes, 0x00020000);
-    if constexpr (kv_gen<BITS>) {
-        stage_gen<BITS>(krs, vrs, tk, tv, tid, kb * kKB, H, h, kz, vz);
-    } else {
-        Raw<BITS> raw;
-        load_raw<BITS>(raw, krs, vrs, tid, kb * kKB, kb * kKB, H, h);
-        store_raw<BITS, VL16>(raw, tk, tv, tid, kz, vz);
+    if (kv_has_share<D>(tid)) {
+        if constexpr (kv_gen<BITS>) {
+            stage_gen<BITS, D>(krs, vrs, tk, tv, tid, kb * kKB, H, h, kz, vz);
+        } else {
+            Raw<BITS> raw;
+            load_raw<BITS, D>(raw, krs, vrs, tid, kb * kKB, kb * kKB, H, h);
+            store_raw<BITS, VL16, D>(raw, tk, tv, tid, kz, vz);
+        }
     }
     __syncthreads();
-    uint8_t *dst = img + (static_cast<size_t>(h) * nkb + kb) * kImg;
+    uint8_t *dst = img + (static_cast<size_t>(h) * nkb + kb) * G::kImg;
     const uint4 *sk = reinterpret_cast<const uint4 *>(&tk[0][0]);
     const uint4 *sv = reinterpret_cast<const uint4 *>(&tv[0][0]);
-    for (int i = tid; i < kKImg / 16; i += 512) reinterpret_cast<uint4 *>(dst)[i] = sk[i];
-    for (int i = tid; i < kVImg / 16; i += 512) reinterpret_cast<uint4 *>(dst + kKImg)[i] = sv[i];
+    for (int i = tid; i < G::kKImg / 16; i += 512) reinterpret_cast<uint4 *>(dst)[i] = sk[i];
+    for (int i = tid; i < G::kVImg / 16; i += 512) reinterpret_cast<uint4 *>(dst + G::kKImg)[i] = sv[i];
 }
 
 // ---- the f32 state (bits 0: the cache's "no decode copy" state, K and V unquantized) ----
@@ -299,14 +327,16 @@ __global__ void kv_f32_params_kernel(const float *__restrict__ red, float *__res
 // The stage pass for f32 K / V: the same thread ownership, LDS tiles and image as kv_stage_kernel
 // (K thread: one key's 32 dims = 128 B; V thread: 4 keys x 8 dims = 4 x 32 B), range-checked buffer
 // loads so that keys at or past S stage as 0 with no memory access.
+template <int D>
 __global__ void __launch_bounds__(512) kv_stage_f32_kernel(const float *__restrict__ K, const float *__restrict__ V,
                                                           const float *__restrict__ params, int S, int H, int nkb,
                                                           uint8_t *__restrict__ img) {
-    __shared__ __attribute__((aligned(16))) _Float16 tk[kKB][kKRow];
-    __shared__ __attribute__((aligned(16))) _Float16 tv[kD][kVRow];
+    using G = AttnGeo<D>;
+    __shared__ __attribute__((aligned(16))) _Float16 tk[kKB][G::kKRow];
+    __shared__ __attribute__((aligned(16))) _Float16 tv[D][kVRow];
     const int tid = threadIdx.x, kb = blockIdx.x, h = blockIdx.y;
     const float kinv = 1.0f / params[0], vinv = 1.0f / params[2];   // exact: powers of two
-    const int nbytes = static_cast<int>(static_cast<size_t>(S) * H * kD * 4);
+    const int nbytes = static_cast<int>(static_cast<size_t>(S) * H * D * 4);
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(K), 0, nbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(V), 0, nbytes, 0x00020000);
     auto load8 = [](__amdgpu_buffer_rsrc_t rs, uint32_t off, float inv) {   // 8 floats -> 8 scaled halves
@@ -318,28 +348,29 @@ __global__ void __launch_bounds__(512) kv_stage_f32_kernel(const float *__restri
         for (int j = 0; j < 8; ++j) o[j] = static_cast<_Float16>(x[j] * inv);   // RNE
         return o;
     };
-    if (tid < 256) {
-        const int key = tid >> 2, d0 = 32 * (tid & 3);
-        const uint32_t off = (static_cast<uint32_t>(kb * kKB + key) * H + h) * (kD * 4) + d0 * 4;
+    const bool mine = kv_has_share<D>(tid);
+    if (mine && tid < 256) {
+        const int key = tid / kKThr<D>, d0 = 32 * (tid % kKThr<D>);
+        const uint32_t off = (static_cast<uint32_t>(kb * kKB + key) * H + h) * (D * 4) + d0 * 4;
 #pragma unroll
         for (int g = 0; g < 4; ++g) *reinterpret_cast<half8_t *>(&tk[key][d0 + 8 * g]) = load8(krs, off + 32 * g, kinv);
-    } else {
-        const int t = tid - 256, k4 = 4 * (t >> 4), d0 = 8 * (t & 15);
+    } else if (mine) {
+        const int t = tid - 256, k4 = 4 * (t / kVThr<D>), d0 = 8 * (t % kVThr<D>);
         half8_t v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            v[i] = load8(vrs, (static_cast<uint32_t>(kb * kKB + k4 + i) * H + h) * (kD * 4) + d0 * 4, vinv);
+            v[i] = load8(vrs, (static_cast<uint32_t>(kb * kKB + k4 + i) * H + h) * (D * 4) + d0 * 4, vinv);
         const int kp4 = (k4 & ~15) | kv_pos(k4 & 15);   // as store_raw
 #pragma unroll
         for (int dd = 0; dd < 8; ++dd)
             *reinterpret_cast<half4_t *>(&tv[d0 + dd][kp4]) = half4_t{v[0][dd], v[1][dd], v[2][dd], v[3][dd]};
     }
     __syncthreads();
-    uint8_t *dst = img + (static_cast<size_t>(h) * nkb + kb) * kImg;
+    uint8_t *dst = img + (static_cast<size_t>(h) * nkb + kb) * G::kImg;
     const uint4 *sk = reinterpret_cast<const uint4 *>(&tk[0][0]);
     const uint4 *sv = reinterpret_cast<const uint4 *>(&tv[0][0]);
-    for (int i = tid; i < kKImg / 16; i += 512) reinterpret_cast<uint4 *>(dst)[i] = sk[i];
-    for (int i = tid; i < kVImg / 16; i += 512) reinterpret_cast<uint4 *>(dst + kKImg)[i] = sv[i];
+    for (int i = tid; i < G::kKImg / 16; i += 512) reinterpret_cast<uint4 *>(dst)[i] = sk[i];
+    for (int i = tid; i < G::kVImg / 16; i += 512) reinterpret_cast<uint4 *>(dst + G::kKImg)[i] = sv[i];
 }
 
 #if DLLM_LAB   // attention v4 (the unscheduled form of v5; A/B and ablation masks)
@@ -385,15 +416,23 @@ __device__ __forceinline__ float swap_halves_sum(float x) {
 #endif
 constexpr bool kAttnBdma = DLLM_ATTN_BDMA != 0;
 
-template <int LAB = 0, bool STAG = false>
+//
+// Head dim D (64 or 128): a region has D / 8 MFMAs (2 x D / 16 of S^T, 4 x D / 32 of P V) and the
+// softmax's VALU work does not depend on D, so the VALU per MFMA of both pipelines is 80 / (D / 8):
+// the 5 of D = 128, and 10 at D = 64, where the region is bound by VALU issue, not by the matrix pipe.
+template <int LAB = 0, bool STAG = false, int D = 128>
 __global__ void __launch_bounds__(kWaves * 64)
 kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__ img, const float *__restrict__ kp,
                     const float *__restrict__ vp, int Sq, int Skv, int H, _Float16 *__restrict__ O) {
     // Sq query rows (the Q load clamp, the O store mask, the grid) against Skv keys (the image blocks,
     // the last block's mask): a block of new tokens attends the whole cache.
+    using G = AttnGeo<D>;
+    constexpr int kD = D, kKRow = G::kKRow, kKImg = G::kKImg, kVImg = G::kVImg, kImg = G::kImg;
+    constexpr int kMfma = kD / 8;             // MFMAs per scheduling region
+    constexpr int kValuPer = 80 / kMfma;      // VALU instructions placed behind each
     constexpr int NB = STAG ? 3 : 2;
     const int nkb = (Skv + kKB - 1) / kKB;
-    __shared__ __attribute__((aligned(16))) AttnSmemN<NB> sm;
+    __shared__ __attribute__((aligned(16))) AttnSmemD<D, NB> sm;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = blockIdx.y;
     const int q0 = blockIdx.x * kQT + wave * 32;
@@ -574,10 +613,10 @@ kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__
         }
         __builtin_amdgcn_sched_group_barrier(0x100, 4, 1);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
+        for (int i = 0; i < kMfma; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
-            __builtin_amdgcn_sched_group_barrier(0x002, 5, 1);
+            __builtin_amdgcn_sched_group_barrier(0x002, kValuPer, 1);
         }
         // Keep the softmax in region 1: without these the compiler sinks the 32 exponentials (and
         // their fmas) past the O-rescale branch into region 2, where they run back to back ahead of
@@ -638,9 +677,9 @@ kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__
         l_run = l_run * alpha + swap_halves_sum(ls[0]);
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 2);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
+        for (int i = 0; i < kMfma; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 2);
-            __builtin_amdgcn_sched_group_barrier(0x002, 5, 2);
+            __builtin_amdgcn_sched_group_barrier(0x002, kValuPer, 2);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 2);
         }
         if constexpr (!(LAB & 256)) __builtin_amdgcn_s_setprio(0);
@@ -685,10 +724,11 @@ kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_wave_barrier();
     if constexpr (!(LAB & (4096 | 32)) && !STAG) {
-        // The wave's 32 x 128 f16 tile goes through the drained K/V ring (every wave passed the loop's
-        // last barrier, so nothing reads it any more; rows padded to 272 B so the two half-waves'
-        // rows land 16 banks apart) and leaves as whole 256-B rows in 16-B lane pieces: 8 global
-        // stores per lane instead of 64 two-byte ones (guide T21).
+        // The wave's 32 x D f16 tile goes through the drained K/V ring (every wave passed the loop's
+        // last barrier, so nothing reads it any more; rows padded to 272 B, or 144 B at D = 64, so the
+        // two half-waves' rows land 16 banks apart; at D = 64 the 8 tiles fill the ring exactly) and
+        // leaves as whole 2 D-byte rows in 16-B lane pieces: D / 16 global stores per lane instead
+        // of D / 2 two-byte ones (guide T21).
         static_assert(kWaves * 32 * kKRow * 2 <= sizeof(sm.k) + sizeof(sm.vt), "O staging must fit the K/V ring");
         _Float16 *tile = reinterpret_cast<_Float16 *>(&sm) + wave * 32 * kKRow;
 #pragma unroll
@@ -706,8 +746,8 @@ kv_attention5_kernel(const _Float16 *__restrict__ Q, const uint8_t *__restrict__
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int c = it * 64 + lane, r = c >> 4, cc = c & 15;
+        for (int it = 0; it < kD / 16; ++it) {
+            const int c = it * 64 + lane, r = c / (kD / 8), cc = c % (kD / 8);
             if (q0 + r < Sq)
                 *reinterpret_cast<u32x4_t *>(O + (static_cast<size_t>(q0 + r) * H + h) * kD + 8 * cc) =
                     *reinterpret_cast<const u32x4_t *>(tile + r * kKRow + 8 * cc);
@@ -749,17 +789,18 @@ using namespace dllm;
 
 namespace {
 
-template <int BITS>
+template <int BITS, int D>
 void launch_stage(dim3 sgrid, hipStream_t st, const uint8_t *Kq, const float *kp, const uint8_t *Vq, const float *vp,
                   int Skv, int H, int nkb, uint8_t *img) {
-    kv_stage_kernel<BITS><<<sgrid, 512, 0, st>>>(Kq, kp, Vq, vp, Skv, H, nkb, img);
+    kv_stage_kernel<BITS, false, D><<<sgrid, 512, 0, st>>>(Kq, kp, Vq, vp, Skv, H, nkb, img);
 }
 
-// Both entry points past their width checks.  bits 1..8: Kv / Vv are packed codes with device params;
+// The entry points past their head-dim and width checks.  bits 1..8: Kv / Vv are packed codes with device params;
 // bits 0: device f32 tensors, staged with the power-of-two params this call writes to its workspace.
+template <int D>
 int kv_attention_launch(const void *Q, size_t Sq, const void *Kv, const float *k_params, const void *Vv,
                         const float *v_params, uint8_t bits, size_t Skv, size_t H, void *O, dllm_stream_t stream) {
-    const size_t D = kD;
+    constexpr int kImg = AttnGeo<D>::kImg;
     const uint8_t *Kq = static_cast<const uint8_t *>(Kv), *Vq = static_cast<const uint8_t *>(Vv);
     if (Sq == 0 || H == 0) return DLLM_OK;
     if (Skv == 0) return fail(DLLM_ERR_INVALID_PARAMS, "dllm_kv_attention: no keys (softmax over an empty set)");
@@ -773,17 +814,17 @@ int kv_attention_launch(const void *Q, size_t Sq, const void *Kv, const float *k
     hipStream_t st = as_stream(stream);
     const int nkb = static_cast<int>((Skv + kKB - 1) / kKB);
     // the attention kernel stages a head's f16 K / V images through one buffer descriptor with
-    // 32-bit offsets (blk * kImg): a head's images must stay below 2 GiB too (~560 B per key, so
-    // S past ~3.8 M keys at small H would pass the code-size check above)
+    // 32-bit offsets (blk * kImg): a head's images must stay below 2 GiB too (~560 B per key at
+    // D = 128, so S past ~3.8 M keys at small H would pass the code-size check above)
     if (static_cast<size_t>(nkb) * kImg >= (size_t{1} << 31))
         return fail(DLLM_ERR_SHAPE_MISMATCH, "a head's K/V images must stay below 2 GiB (32-bit buffer offsets)");
     uint8_t *img = reinterpret_cast<uint8_t *>(device_workspace(st, static_cast<size_t>(H) * nkb * kImg, 8));
     if (!img) return DLLM_ERR_HIP;
     dim3 sgrid(static_cast<unsigned>(nkb), static_cast<unsigned>(H));
 #if DLLM_LAB
-    // The A/B schedules are single-S kernels fed by the 4- and 8-bit stage pass: every other width and
-    // every Sq != Skv call runs the product kernel.
-    const int lab = (Sq == Skv && (bits == 4 || bits == 8))
+    // The A/B schedules are single-S, D = 128 kernels fed by the 4- and 8-bit stage pass: every other
+    // width, every Sq != Skv call and D = 64 run the product kernel.
+    const int lab = (D == 128 && Sq == Skv && (bits == 4 || bits == 8))
                         ? [] { const char *e = getenv("DLLM_ATTN_LAB"); return e ? atoi(e) : 0; }() : 0;
 #endif
     if (bits == 0) {
@@ -798,7 +839,7 @@ int kv_attention_launch(const void *Q, size_t Sq, const void *Kv, const float *k
         if (rc) return rc;
         kv_f32_params_kernel<<<1, 64, 0, st>>>(aux + 4, aux);
         DLLM_LAUNCH_CHECK();
-        kv_stage_f32_kernel<<<sgrid, 512, 0, st>>>(Kf, Vf, aux, (int)Skv, (int)H, nkb, img);
+        kv_stage_f32_kernel<D><<<sgrid, 512, 0, st>>>(Kf, Vf, aux, (int)Skv, (int)H, nkb, img);
         k_params = aux;
         v_params = aux + 2;
     } else
@@ -809,14 +850,14 @@ int kv_attention_launch(const void *Q, size_t Sq, const void *Kv, const float *k
     } else
 #endif
     switch (bits) {
-        case 1: launch_stage<1>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
-        case 2: launch_stage<2>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
-        case 3: launch_stage<3>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
-        case 4: launch_stage<4>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
-        case 5: launch_stage<5>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
-        case 6: launch_stage<6>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
-        case 7: launch_stage<7>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
-        default: launch_stage<8>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 1: launch_stage<1, D>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 2: launch_stage<2, D>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 3: launch_stage<3, D>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 4: launch_stage<4, D>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 5: launch_stage<5, D>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 6: launch_stage<6, D>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        case 7: launch_stage<7, D>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
+        default: launch_stage<8, D>(sgrid, st, Kq, k_params, Vq, v_params, (int)Skv, (int)H, nkb, img); break;
     }
     DLLM_LAUNCH_CHECK();
     dim3 grid(static_cast<unsigned>((Sq + kQT - 1) / kQT), static_cast<unsigned>(H));
@@ -865,11 +906,11 @@ int kv_attention_launch(const void *Q, size_t Sq, const void *Kv, const float *k
             kv_attention5_kernel<0, true><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
             break;
         default:
-            kv_attention5_kernel<0, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
+            kv_attention5_kernel<0, false, D><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
             break;
     }
 #else
-    kv_attention5_kernel<0, false><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
+    kv_attention5_kernel<0, false, D><<<grid, kWaves * 64, 0, st>>>(Qh, img, k_params, v_params, (int)Sq, (int)Skv, (int)H, Oh);
 #endif
     DLLM_LAUNCH_CHECK();
     return DLLM_OK;
@@ -877,19 +918,29 @@ int kv_attention_launch(const void *Q, size_t Sq, const void *Kv, const float *k
 
 }  // namespace
 
+extern "C" int dllm_kv_attention_hd(const void *Q, size_t Sq, const void *K, const float *k_params, const void *V,
+                                    const float *v_params, uint8_t bits, size_t Skv, size_t H, size_t D, void *O,
+                                    dllm_stream_t stream) {
+    if (D != 64 && D != 128) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention_hd: head dim must be 64 or 128");
+    if (bits > 8) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention_hd: bits must be 0 (f32 K/V) or 1..8");
+    return D == 64 ? kv_attention_launch<64>(Q, Sq, K, k_params, V, v_params, bits, Skv, H, O, stream)
+                   : kv_attention_launch<128>(Q, Sq, K, k_params, V, v_params, bits, Skv, H, O, stream);
+}
+
+// The D == 128 case of the same launcher (its refusal as it always was).
 extern "C" int dllm_kv_attention_ex(const void *Q, size_t Sq, const void *K, const float *k_params, const void *V,
                                     const float *v_params, uint8_t bits, size_t Skv, size_t H, size_t D, void *O,
                                     dllm_stream_t stream) {
-    if (D != kD) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention_ex: head dim must be 128");
+    if (D != 128) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention_ex: head dim must be 128");
     if (bits > 8) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention_ex: bits must be 0 (f32 K/V) or 1..8");
-    return kv_attention_launch(Q, Sq, K, k_params, V, v_params, bits, Skv, H, O, stream);
+    return kv_attention_launch<128>(Q, Sq, K, k_params, V, v_params, bits, Skv, H, O, stream);
 }
 
 // The Sq == Skv == S, bits in {4, 8} case of the same launcher (its refusals as they always were).
 extern "C" int dllm_kv_attention(const void *Q, const uint8_t *Kq, const float *k_params, const uint8_t *Vq,
                                  const float *v_params, uint8_t bits, size_t S, size_t H, size_t D, void *O,
                                  dllm_stream_t stream) {
-    if (D != kD) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention: head dim must be 128");
+    if (D != 128) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention: head dim must be 128");
     if (bits != 4 && bits != 8) return fail(DLLM_ERR_UNSUPPORTED, "dllm_kv_attention: bits must be 4 or 8");
-    return kv_attention_launch(Q, S, Kq, k_params, Vq, v_params, bits, S, H, O, stream);
+    return kv_attention_launch<128>(Q, S, Kq, k_params, Vq, v_params, bits, S, H, O, stream);
 }

@@ -307,7 +307,7 @@ class KVCacheEntry:
         return t.dequantize().reshape(t.shape)
 
     def attention(self, q: torch.Tensor, layer: int = 0) -> torch.Tensor:
-        """Dequant-attention of ``q`` f16 [Sq, H, 128] (H * 128 == hidden) to layer ``layer``'s K/V
+        """Dequant-attention of ``q`` f16 [Sq, H, D] (H * D == hidden, D = 64 or 128) to layer ``layer``'s K/V
         in the state the entry is in -- the data ``get_keys()[layer]`` / ``get_values()[layer]``
         hand out: the prefill copy, the decode copy at its current progressive width, or the f32
         tensors when there is no copy (width 0) -- read in place, nothing dequantized to HBM."""

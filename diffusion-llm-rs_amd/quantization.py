@@ -372,15 +372,16 @@ class QuantizedKVCacheEntry:
 
 
 def kv_attention(q: torch.Tensor, keys, values, *, offset: int = 0, skv: int | None = None) -> torch.Tensor:
-    """KV dequant-attention (a9, dllm_kv_attention_ex): O = softmax(Q K^T / sqrt(D)) V per head, q f16
-    [Sq, H, 128] -> O f16 [Sq, H, 128], against all Skv keys of a cache in any of its states:
+    """KV dequant-attention (a9, dllm_kv_attention_hd): O = softmax(Q K^T / sqrt(D)) V per head, q f16
+    [Sq, H, D] -> O f16 [Sq, H, D] with D = 64 or 128 (any other D raises ``UnsupportedOperation``),
+    against all Skv keys of a cache in any of its states:
 
     * ``keys`` / ``values`` packed :class:`QuantizedTensor` of one width 1..8 (the per-tensor
       quantized copies of ``QuantizedKVCacheEntry``), dequantized inside the kernel, or
     * f32 device tensors (the cache's "no decode copy" state), staged as f16 with one power-of-two
       scale per tensor (include/dllm_quant.h).
 
-    K and V are the ``[Skv, H, 128]`` elements ``offset .. offset + Skv * H * 128`` of the flattened
+    K and V are the ``[Skv, H, D]`` elements ``offset .. offset + Skv * H * D`` of the flattened
     tensors, read in place: ``offset = layer * seq * hidden, skv = seq`` addresses one layer of a
     ``[layers, seq, hidden]`` cache tensor.  By default Skv is every whole row from ``offset`` on.
     The slice must start on a 16-byte boundary of the code stream (any layer of a cache does)."""
@@ -414,7 +415,7 @@ def kv_attention(q: torch.Tensor, keys, values, *, offset: int = 0, skv: int | N
     byte_off //= 8
     qd = _dev(q, torch.float16)
     out = torch.empty(Sq, H, D, dtype=torch.float16, device=qd.device)
-    check(_lib.load().dllm_kv_attention_ex(_ptr(qd), Sq, kd.data_ptr() + byte_off, _ptr(kp), vd.data_ptr() + byte_off,
+    check(_lib.load().dllm_kv_attention_hd(_ptr(qd), Sq, kd.data_ptr() + byte_off, _ptr(kp), vd.data_ptr() + byte_off,
                                            _ptr(vp), bits, skv, H, D, _ptr(out), _stream()))
     return out
 

@@ -391,11 +391,23 @@ int dllm_kv_attention(const void *Q, const uint8_t *Kq, const float *k_params, c
  *   16-byte aligned -> DLLM_ERR_INVALID_PARAMS; K or V of 2 GiB or more (4 bytes per element for
  *   bits 0) -> DLLM_ERR_SHAPE_MISMATCH.
  * Asynchronous on `stream`, never synchronises.  The only allocations are the grow-only per-stream
- * workspaces (the images, H * ceil(Skv/64) * 35 KiB; for bits 0 also a few KiB for the extremes and
+ * workspaces (the images, H * ceil(Skv/64) * 35 KiB, or 18 KiB at D == 64 through
+ * dllm_kv_attention_hd; for bits 0 also a few KiB for the extremes and
  * the params), made on the first call of a shape: capture-safe once a shape has run.
  * dllm_kv_attention is the Sq == Skv == S, bits in {4, 8} case of the same launcher and refuses
  * every other width as it always did. */
 int dllm_kv_attention_ex(const void *Q, size_t Sq, const void *K, const float *k_params, const void *V,
+                         const float *v_params, uint8_t bits, size_t Skv, size_t H, size_t D, void *O,
+                         dllm_stream_t stream);
+/* dllm_kv_attention_ex for D == 64 or D == 128: the same arguments, contract and launcher, one kernel
+ * instantiation per head dim.  D == 64 is the head dim of the reference's default configuration
+ * (hidden_size 768 / num_attention_heads 12, diffuse-llm-rs/src/lib.rs:477-482, :958-966).  Every
+ * other D -> DLLM_ERR_UNSUPPORTED, checked like bits > 8 before anything touches the device.  At
+ * D == 128 the result is dllm_kv_attention_ex's, byte for byte.  The image workspace is
+ * H * ceil(Skv/64) * 18 KiB at D == 64 (35 KiB at D == 128); K or V of 2 GiB or more, or a head's
+ * images of 2 GiB or more -> DLLM_ERR_SHAPE_MISMATCH.  dllm_kv_attention_ex and dllm_kv_attention
+ * keep refusing D != 128 as they always did. */
+int dllm_kv_attention_hd(const void *Q, size_t Sq, const void *K, const float *k_params, const void *V,
                          const float *v_params, uint8_t bits, size_t Skv, size_t H, size_t D, void *O,
                          dllm_stream_t stream);
 
