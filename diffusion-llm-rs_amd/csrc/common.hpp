@@ -9,6 +9,7 @@
 #include <string>
 
 #include "dllm_quant.h"
+#include "plan_consts.hpp"   // kWave, kCUs, kXCDs and the linear layer's host-visible constants
 
 // Streaming (non-temporal) stores for the GEMMs' f16 tile rows (whole 512-B rows per instruction;
 // A/B builds: -DDLLM_NT_STORE=0).  Not for the dequantize outputs: there the same hint is 1.1-2.7x
@@ -89,10 +90,6 @@ __device__ __forceinline__ void bload16_asm(u32x4_t &d, __amdgpu_buffer_rsrc_t r
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void *base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0x7FFFFFFF, 0x00020000);
 }
-
-constexpr int kWave = 64;      // CDNA wavefront width
-constexpr int kCUs = 256;      // MI355X compute units (8 XCDs x 32)
-constexpr int kXCDs = 8;
 
 inline unsigned grid_for(size_t work_items, int block, unsigned cap = kCUs * 8) {
     size_t g = (work_items + block - 1) / block;

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.hpp"
 #include "diffusion_rng.hpp"
+#include "linear_plan.hpp"   // the kernel selection the launchers switch on (host-only)
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
@@ -26,7 +27,7 @@ struct PSampleEpi {
 
 namespace {
 
-constexpr int kBM = 256, kBN = 128, kBK = 64, kThreads = 256;
+constexpr int kBM = 256, kThreads = 256;   // kBN, kBK: plan_consts.hpp
 
 // Four consecutive outputs (element i = m N + n .. + 3) of the fused epilogue with x_t[i..i+3] and
 // the row's coefficients already loaded: a caller that hoists every tile load above the tile's
@@ -332,13 +333,9 @@ struct ExactGemmArgs {
     const PSampleEpi *epi;
     int tm = 0;   // A/B: 256 x 256 tile-major tiles where they fill the chip
     int lab_policy = 0;   // lab A/B: 1 = the round-2 tile policy (no 32 x 128 mid-M tiles)
-    const float *hr = nullptr;   // Horner ratios (DLLM_EXACT_HORNER builds: the 128 x 256 tiles in Horner form)
 };
+// Switches on exact_plan (linear_plan.hpp); needs exact_gemm_supported(M, K, Npad, group).
 int launch_exact_gemm(const ExactGemmArgs &a, int y_f32, hipStream_t st);
-// The fold-form tile selection (the one routine launch_exact_gemm switches on and dllm_linear_plan
-// reports): fills tile_m, tile_n, kgroups, nsplit and flags of a DLLM_KERNEL_EXACT_FOLD plan.  Host
-// arithmetic only.  Needs exact_gemm_supported(M, K, Npad, group).
-void select_exact_plan(int bits, int M, int K, int Npad, int group, dllm_linear_plan_t *p);
 
 // Exact-weight int4 g128 GEMM in Horner form on 256 x 256 tiles (linear_horner.hip): hr = the
 // handle's ratios [G + 1][Npad], sf = its f32 scales (the last group's multiply the result).
@@ -367,7 +364,6 @@ int launch_horner_pc_gemm(const HornerGemmArgs &a, int y_f32, hipStream_t st);
 // Its two-k-group form on rows x 128 tiles, rows = 128 / 64 / 32 (linear_pc.hip): needs K % 256 == 0
 // and Npad % 128 == 0.
 int launch_horner_pc_kg2_gemm(const HornerGemmArgs &a, int rows, int y_f32, hipStream_t st);
-bool exact_gemm_supported(int M, int K, int Npad, int group);
 
 // Ping-pong 256 x 256 GEMM (linear_pp.hip): Y = X . W^ + b for the 256-column-tile grid, bits in
 // {2, 4, 8}, Y f16 (y_f32 = 0) or f32, epi != null: fused p_sample epilogue into epi->x_prev.

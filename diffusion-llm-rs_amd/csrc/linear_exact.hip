@@ -21,53 +21,25 @@
 #include "linear_common.hpp"
 #include "stamp.hpp"
 
-#ifndef DLLM_LAB
-#define DLLM_LAB 0
-#endif
-// Policy switches (product defaults; A/B builds flip them, profiles/r02_gemm_ab/):
-// DLLM_EXACT_WREG = 1: int4 weight words go global -> VGPR (buffer_load_dwordx4 from inline asm,
-//   counted in the same vmcnt waits as the stage's LDS-DMA) instead of through the LDS ring: each
-//   wave's slab words are its own (bit-identical; -0.5 %, and 16 KiB less LDS per stage).
-// DLLM_EXACT_KG2 = 1: tile-starved grids (column shards) run 128 x 128 or 64 x 128 tiles with two
-//   k-groups of 4 waves per block (4096 x 1024: 45.0 -> 40.5 us; 4096 x 512: 32.0 -> 24.4 us).
-// DLLM_EXACT_MR2 = 1: grids still short of a round get 64 x 128 tiles (two blocks per CU).
+// Settled forms (measured, profiles/r02_gemm_ab/ unless named; the tile policy itself: exact_plan,
+// linear_plan.cpp):
+// - int4 weight words go global -> VGPR (WREG: buffer_load_dwordx4 from inline asm, counted in the
+//   same vmcnt waits as the stage's LDS-DMA) instead of through the LDS ring: each wave's slab
+//   words are its own (bit-identical; -0.5 %, and 16 KiB less LDS per stage).
+// - The 128 x 256 int4 g128 tiles run their two wave halves half a step apart (STAG; M 2048 / 3072 x
+//   4096: 76.9 -> 73.9 / 121.6 -> 114.0 us, same bits).  The k-group tiles with their k-group halves
+//   staggered measured 2-7 % slower (4096 x 1024 / 512, 256 / 512 x 4096) and stay unstaggered, and
+//   the staggered tiles on 16x16x32 MFMAs measured within +-1.5 % (mixed sign) of these
+//   (profiles/r05_stag).
+// - Not adopted: two groups per stage in a 2-stage ring (one barrier per two groups) spills at
+//   256 VGPRs (a build without the per-stage barrier is only 8 % faster); the fold kernels on
+//   16x16x32 MFMAs (S16) are bit-exact on the policy grid but no faster (M 2048 x 4096: 75.7 vs
+//   77.4 us; the 4-GPU shard 4096 x 1024 42.7 vs 42.0; 4096 x 512 26.7 vs 24.6;
+//   profiles/r04_shard/exact_s16_ab.jsonl), so the product keeps the 32x32x16 form here (the Horner
+//   kernel's 16x16x32 form wins on 3 of 4 boxes).
 // DLLM_EXACT_PRIO = 0 drops the s_setprio raise around the MFMA sections (measured 1 % slower).
-// DLLM_EXACT_RING2 = 1: two groups per stage in a 2-stage ring (one barrier per two groups):
-//   spills at 256 VGPRs, not adopted (a build without the per-stage barrier is only 8 % faster).
-#ifndef DLLM_EXACT_WREG
-#define DLLM_EXACT_WREG 1
-#endif
 #ifndef DLLM_EXACT_PRIO
 #define DLLM_EXACT_PRIO 1
-#endif
-#ifndef DLLM_EXACT_MR2
-#define DLLM_EXACT_MR2 1
-#endif
-#ifndef DLLM_EXACT_RING2
-#define DLLM_EXACT_RING2 0
-#endif
-// DLLM_EXACT_S16 = 1: the fold kernels on 16x16x32 MFMAs (A/B builds only).  Bit-exact on the policy
-// grid, but no faster on the box measured (M 2048 x 4096: 75.7 vs 77.4 us; the 4-GPU shard 4096 x 1024
-// 42.7 vs 42.0; 4096 x 512 26.7 vs 24.6; profiles/r04_shard/exact_s16_ab.jsonl), so the product keeps
-// the 32x32x16 form here (the Horner kernel's 16x16x32 form wins on 3 of 4 boxes).
-#ifndef DLLM_EXACT_S16
-#define DLLM_EXACT_S16 0
-#endif
-// DLLM_EXACT_STAG = 1: the 128 x 256 int4 g128 tiles run their two wave halves half a step apart
-// (M 2048 / 3072 x 4096: 76.9 -> 73.9 / 121.6 -> 114.0 us, same bits).  The k-group tiles with
-// their k-group halves staggered measured 2-7 % slower (4096 x 1024 / 512, 256 / 512 x 4096) and
-// stay unstaggered, and the staggered tiles on 16x16x32 MFMAs measured within +-1.5 % (mixed
-// sign) of these (profiles/r05_stag).
-#ifndef DLLM_EXACT_STAG
-#define DLLM_EXACT_STAG 1
-#endif
-#ifndef DLLM_EXACT_KG2
-#define DLLM_EXACT_KG2 1
-#endif
-// Horner form on the 128 x 256 tiles (A/B): one accumulator rescaled by s_{g-1}/s_g at each group
-// head instead of the transient group sum and its fold (see wq_gemm8_kernel<..., HORNER>).
-#ifndef DLLM_EXACT_HORNER
-#define DLLM_EXACT_HORNER 0
 #endif
 
 // DLLM_EXACT_KG_COAL = 1: on the k-group tiles (KG >= 2) the f16 epilogue is the coalesced LDS-staged
@@ -1007,32 +979,22 @@ wq_gemm_exact_kernel(const __half *__restrict__ X, int M, int K, const uint32_t 
 }
 
 template <int BITS, typename YT, int NW, int MR, int SPS, int KPG, int EPI, bool TM = false, int GPS = 1, int RING = 3,
-          int KG = 1, bool WREG = (DLLM_EXACT_WREG != 0 && BITS == 4 && !TM), bool HORN = false,
-          bool S16 = (DLLM_EXACT_S16 != 0 && !TM && !HORN), bool STAG = false>
+          int KG = 1, bool WREG = BITS == 4 && !TM, bool STAG = false>
 int launch_exact_tile(const ExactGemmArgs &a, int nsplit, hipStream_t st) {
-    if constexpr (HORN) {
-        const int nbm = (a.M + 32 * MR - 1) / (32 * MR), nbn = a.Npad / (32 * NW);
-        const PSampleEpi ep = a.epi ? *a.epi : PSampleEpi{};
-        wq_gemm_exact_kernel<BITS, YT, NW, MR, SPS, KPG, false, EPI, false, 1, WREG, GPS, RING, 1, true>
-            <<<static_cast<unsigned>(nbm * nbn), NW * 64, 0, st>>>(a.X, a.M, a.K, a.wdev, a.sz, a.hr, a.bias,
-                                                                    static_cast<YT *>(a.Y), a.N, a.Npad, a.group, nbm, nbn,
-                                                                    1, nullptr, ep, a.sf);
-        DLLM_LAUNCH_CHECK();
-        return DLLM_OK;
-    }
+    // (the kernel's HORN and S16 forms are not instantiated: both arguments stay false)
     const int nbm = (a.M + 32 * MR - 1) / (32 * MR), nbn = a.Npad / (32 * NW);
     const unsigned nb = static_cast<unsigned>(nbm * nbn * nsplit);
     const PSampleEpi ep = a.epi ? *a.epi : PSampleEpi{};
     YT *Y = static_cast<YT *>(a.Y);
     if (nsplit == 1) {
-        wq_gemm_exact_kernel<BITS, YT, NW, MR, SPS, KPG, false, EPI, TM, 1, WREG, GPS, RING, KG, false, S16, STAG><<<nb, NW * KG * 64, 0, st>>>(
+        wq_gemm_exact_kernel<BITS, YT, NW, MR, SPS, KPG, false, EPI, TM, 1, WREG, GPS, RING, KG, false, false, STAG><<<nb, NW * KG * 64, 0, st>>>(
             a.X, a.M, a.K, a.wdev, a.sz, a.sf, a.bias, Y, a.N, a.Npad, a.group, nbm, nbn, 1, nullptr, ep);
         DLLM_LAUNCH_CHECK();
         return DLLM_OK;
     }
     float *ws = device_workspace(st, static_cast<size_t>(nsplit) * a.M * a.Npad * sizeof(float));
     if (!ws) return DLLM_ERR_HIP;
-    wq_gemm_exact_kernel<BITS, YT, NW, MR, SPS, KPG, true, 0, TM, 1, WREG, GPS, RING, KG, false, S16, STAG><<<nb, NW * KG * 64, 0, st>>>(
+    wq_gemm_exact_kernel<BITS, YT, NW, MR, SPS, KPG, true, 0, TM, 1, WREG, GPS, RING, KG, false, false, STAG><<<nb, NW * KG * 64, 0, st>>>(
         a.X, a.M, a.K, a.wdev, a.sz, a.sf, a.bias, Y, a.N, a.Npad, a.group, nbm, nbn, nsplit, ws);
     DLLM_LAUNCH_CHECK();
     const size_t q = static_cast<size_t>(a.M) * (a.Npad / 4);
@@ -1042,122 +1004,47 @@ int launch_exact_tile(const ExactGemmArgs &a, int nsplit, hipStream_t st) {
     return DLLM_OK;
 }
 
-// Tile policy (G64 = group / 64):
-// 1. 128 x 256 tiles (8 waves, two per SIMD; stages of one 128-row group) when they give >= 256 blocks;
-// 2. (int4, group 128, KG2) 128 x 128 tiles with two k-groups per block when those give 256..511
-//    blocks, else 64 x 128 tiles with two k-groups when those give >= 256;
-// 3. (MR2) 64 x 128 tiles (4 waves) while 128 x 128 tiles give < 512 blocks, K split until >= 512;
-// 4. 128 x 128 tiles (4 waves, two blocks per CU, 64-deep stages) with K split over group-aligned
-//    slices until the grid has >= ~200 blocks.
+// Which tile a (shape, M) runs: exact_plan (linear_plan.cpp); launch_exact_bits maps each plan to
+// its template arguments.
 // Mid-M 32 x 128 tiles: LDS stages in the ring (10 KiB each; the weight words ride in VGPRs).
 // Deeper rings keep more of a block's 512 KiB (X + weight words at K = 4096) in flight but measured
 // no gain (M 256 / 384: RING 3 / 4 / 6 / 8 = 20.6 / 20.6 / 20.4 / 20.8 and 24.6 / 24.0 / 24.5 / 26.3
 // us, profiles/r03_midm/ring_depth.jsonl): the single wave per SIMD is issue/latency bound, not
 // fed short of bytes.
 constexpr int kMidRing = 3;
-// The mid-M tiles also where their grid is short of a round (DLLM_MIDM_MINFILL tiles and more): one
-// 32 x 128 tile per CU takes the same time whether 96 or 256 CUs have one.  N 4096, 40-layer chain:
-// M 65 / 96 / 128 / 160 / 192 / 224 = 16.5 / 18.2 / 20.4 / 23.1 / 24.6 / 23.5 -> 15.4 / 17.2 / 17.1 /
-// 16.5 / 16.6 / 16.5 us against the K-split 64 x 128 tiles (profiles/r06_tiles/midm_short_grid_ab.jsonl);
-// from 48 tiles (narrow N): N 2048 M 128 15.0 -> 13.2, N 1024 M 256 14.9 -> 13.2, N 512 M 384 / 512
-// 13.7 / 15.0 -> 13.2 / 13.2 us, nothing slower (profiles/r06_tiles/m48/).
-#ifndef DLLM_MIDM_MINFILL
-#define DLLM_MIDM_MINFILL 48
-#endif
-
-// The product selection above as one host routine (select_exact_plan, below the namespace) that
-// launch_exact_bits switches on; the template arguments each plan maps to are the launcher's.
-inline void exact_plan(int bits, int M, int K, int Npad, int group, dllm_linear_plan_t *p) {
-    const int g64 = group / kBK, mb = (M + 127) / 128;
-    // the int4 g128 forms: weight words in registers (WREG)
-    const bool i4g128 = g64 == 2 && bits == 4 && DLLM_EXACT_WREG;
-    auto set = [&](int tm, int tn, int kg, int ns, int flags) {
-        p->kernel = DLLM_KERNEL_EXACT_FOLD;
-        p->tile_m = tm; p->tile_n = tn; p->kgroups = kg; p->nsplit = ns;
-        p->flags = flags | (ns > 1 ? DLLM_PLAN_SPLITK : 0);
-    };
-    if (Npad % 256 == 0 && mb * (Npad / 256) >= kCUs) {
-        const bool stag = DLLM_EXACT_STAG && i4g128 && !DLLM_EXACT_S16 && !DLLM_EXACT_RING2 && !DLLM_EXACT_HORNER;
-        return set(128, 256, 1, 1, stag ? DLLM_PLAN_STAGGERED : 0);
-    }
-    const int tiles = mb * (Npad / 128), ngroups = K / group;
-    const int t64 = ((M + 63) / 64) * (Npad / 128);
-    // Mid M (int4 g128): 32 x 128 tiles of 4 waves streaming the whole K -- no K split, hence no
-    // f32 slabs and no combine launch -- where they give a full round but 64 x 128 tiles do not
-    // (M 225..448 at N = 4096, where the policy below splits K): M 256 / 384: 25.1 -> 20.4 /
-    // 30.0 -> 24.6 us; at M >= 512 the 64 x 128 two-k-group tiles stay faster (23.1 vs 25.8 us)
-    // (profiles/r03_midm/policy_ab.json).
-    if (i4g128) {
-        const int t32 = ((M + 31) / 32) * (Npad / 128);
-        if (tiles < kCUs && t64 < kCUs && t32 >= DLLM_MIDM_MINFILL) {
-            // k-groups of 4 waves sharing the tile (k-group g streams the g-th part of K; sums handed
-            // to k-group 0 through the ring): four (16 waves, one block per CU) while the grid is
-            // one block per CU, else two (8 waves, two blocks per CU fit).  M 256: 20.4 (one
-            // k-group) -> 15.5 (two) -> 14.3 us (four); M 384: 24.5 -> 22.1 (two) / 25.1 (four)
-            // (profiles/r03_midm/kgroups.jsonl).
-            if (t32 <= kCUs && ngroups % 4 == 0) return set(32, 128, 4, 1, 0);
-            if (ngroups % 2 == 0) return set(32, 128, 2, 1, 0);
-            return set(32, 128, 1, 1, 0);
-        }
-    }
-    // tile-starved grids: 128 x 128 (or 64 x 128) tiles with two k-groups of 4 waves per block
-    if (DLLM_EXACT_KG2 && i4g128) {
-        if (tiles >= kCUs && tiles < 2 * kCUs && ngroups % 2 == 0) return set(128, 128, 2, 1, 0);
-        if (tiles < kCUs && t64 >= kCUs && ngroups % 2 == 0) return set(64, 128, 2, 1, 0);
-    }
-    if (DLLM_EXACT_MR2 && tiles < 2 * kCUs) {
-        int ns = 1;
-        while (t64 * ns < 2 * kCUs && ns < 8 && ngroups % (2 * ns) == 0 && (K / kBK) / (2 * ns) >= 4) ns *= 2;
-        return set(64, 128, 1, ns, 0);
-    }
-    int nsplit = 1;
-    while (tiles * nsplit < 200 && nsplit < 8 && ngroups % (2 * nsplit) == 0 && (K / kBK) / (2 * nsplit) >= 4)
-        nsplit *= 2;
-    return set(128, 128, 1, nsplit, 0);
-}
 
 #if DLLM_LAB
 // Lab A/B overrides of the tile policy (ExactGemmArgs::tm, lab_policy), applied after the product
-// plan: -1 = no override for this shape (the product plan runs).
+// plan: -1 = no override for this shape (the product plan runs).  The thresholds are the product
+// plan's own (exact_grids).
 template <int BITS, typename YT, int G64, int EPI>
 int launch_exact_lab(const ExactGemmArgs &a, hipStream_t st) {
-    const int mb = (a.M + 127) / 128;
+    const ExactGrids g = exact_grids(a.M, a.K, a.Npad, a.group);
     if (a.tm && a.Npad % 256 == 0 && ((a.M + 255) / 256) * (a.Npad / 256) >= kCUs)
         return launch_exact_tile<BITS, YT, 8, 8, 1, G64, EPI, true>(a, 1, st);
-    if (a.lab_policy == 0 || (a.Npad % 256 == 0 && mb * (a.Npad / 256) >= kCUs)) return -1;
-    if constexpr (G64 == 2 && BITS == 4 && DLLM_EXACT_WREG) {
-        const int tiles = mb * (a.Npad / 128), ngroups = a.K / a.group;
-        const int t32 = ((a.M + 31) / 32) * (a.Npad / 128), t64 = ((a.M + 63) / 64) * (a.Npad / 128);
-        const bool mid = tiles < kCUs && t64 < kCUs && t32 >= DLLM_MIDM_MINFILL;
-        if (mid) {
+    if (a.lab_policy == 0 || g.full256) return -1;
+    if constexpr (G64 == 2 && BITS == 4) {
+        if (g.mid) {
             switch (a.lab_policy) {   // lab A/B: one k-group (RING 3) / two k-groups / four (RING 3)
             case 2: return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, kMidRing>(a, 1, st);
-            case 3: if (ngroups % 2 == 0) return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
+            case 3: if (g.ngroups % 2 == 0) return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
                     break;
-            case 4: if (ngroups % 4 == 0) return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 3, 4>(a, 1, st);
+            case 4: if (g.ngroups % 4 == 0) return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, 3, 4>(a, 1, st);
                     break;
             default: break;
             }
             if (a.lab_policy != 1) return -1;
         }
-#if DLLM_EXACT_KG2
         // (policy 5: 64 x 128 tiles, two blocks per CU, where 128 x 128 tiles give one round;
         // 6 / 7: the 128 x 128 tiles with 64-deep stages in a 4- / 3-stage ring instead of 128-deep
         // stages in a 2-stage ring; 1: the round-2 tile policy, no 32 x 128 mid-M tiles)
-        const bool one_round = tiles >= kCUs && tiles < 2 * kCUs && ngroups % 2 == 0;
-        if (one_round && a.lab_policy == 6) return launch_exact_tile<BITS, YT, 4, 4, 1, 2, EPI, false, 1, 4, 2>(a, 1, st);
-        if (one_round && a.lab_policy == 7) return launch_exact_tile<BITS, YT, 4, 4, 1, 2, EPI, false, 1, 3, 2>(a, 1, st);
-        if (one_round && a.lab_policy != 5) return launch_exact_tile<BITS, YT, 4, 4, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
-        if ((tiles < kCUs || a.lab_policy == 5) && t64 >= kCUs && ngroups % 2 == 0)
+        if (g.one_round && a.lab_policy == 6) return launch_exact_tile<BITS, YT, 4, 4, 1, 2, EPI, false, 1, 4, 2>(a, 1, st);
+        if (g.one_round && a.lab_policy == 7) return launch_exact_tile<BITS, YT, 4, 4, 1, 2, EPI, false, 1, 3, 2>(a, 1, st);
+        if (g.one_round && a.lab_policy != 5) return launch_exact_tile<BITS, YT, 4, 4, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
+        if ((g.tiles < kCUs || a.lab_policy == 5) && g.t64 >= kCUs && g.ngroups % 2 == 0)
             return launch_exact_tile<BITS, YT, 4, 2, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
-#endif
-#if DLLM_EXACT_MR2
-        if (mid && tiles < 2 * kCUs) {   // policy 1 on a mid-M grid: the K-split 64 x 128 tiles
-            int ns = 1;
-            while (t64 * ns < 2 * kCUs && ns < 8 && ngroups % (2 * ns) == 0 && (a.K / kBK) / (2 * ns) >= 4) ns *= 2;
-            return launch_exact_tile<BITS, YT, 4, 2, 1, G64, EPI>(a, ns, st);
-        }
-#endif
+        if (g.mid && g.tiles < 2 * kCUs)   // policy 1 on a mid-M grid: the K-split 64 x 128 tiles
+            return launch_exact_tile<BITS, YT, 4, 2, 1, G64, EPI>(a, exact_split64(g, a.K), st);
     }
     return -1;
 }
@@ -1173,28 +1060,14 @@ int launch_exact_bits(const ExactGemmArgs &a, hipStream_t st) {
 #endif
     dllm_linear_plan_t p;
     exact_plan(BITS, a.M, a.K, a.Npad, a.group, &p);
-    constexpr bool kI4G128 = G64 == 2 && BITS == 4 && DLLM_EXACT_WREG;
+    constexpr bool kI4G128 = G64 == 2 && BITS == 4;
     const int ns = p.nsplit;
     if (p.tile_m == 128 && p.tile_n == 256) {
         // int8 weights: one-slab stages (two-slab stages exceed the 160 KiB LDS ring)
         if constexpr (G64 == 1 || BITS == 8) return launch_exact_tile<BITS, YT, 8, 4, 1, G64, EPI>(a, 1, st);
-#if DLLM_EXACT_RING2
-        // two whole 128-row groups per stage, 2-stage ring: one barrier per two groups
-        else if constexpr (G64 == 2 && BITS == 4 && DLLM_EXACT_WREG) return launch_exact_tile<BITS, YT, 8, 4, 4, 1, EPI, false, 2, 2>(a, 1, st);
-#endif
-        else if constexpr (G64 == 2 && BITS == 4 && DLLM_EXACT_HORNER) {
-#if DLLM_EXACT_HORNER == 2   // two groups per stage, 2-stage ring: one barrier per two groups
-            if (a.hr) return launch_exact_tile<BITS, YT, 8, 4, 4, 1, EPI, false, 2, 2, 1, DLLM_EXACT_WREG != 0, true>(a, 1, st);
-#else
-            if (a.hr) return launch_exact_tile<BITS, YT, 8, 4, 2, 1, EPI, false, 1, 3, 1, DLLM_EXACT_WREG != 0, true>(a, 1, st);
-#endif
-            return launch_exact_tile<BITS, YT, 8, 4, 2, 1, EPI>(a, 1, st);
-        }
-#if DLLM_EXACT_STAG
-        // the two wave halves half a step apart (4-slot ring, stage kt + 2 issued in step kt; 136 KiB)
-        else if constexpr (G64 == 2 && BITS == 4 && DLLM_EXACT_WREG && !DLLM_EXACT_S16)
-            return launch_exact_tile<BITS, YT, 8, 4, 2, 1, EPI, false, 1, 4, 1, true, false, false, true>(a, 1, st);
-#endif
+        // DLLM_PLAN_STAGGERED: the two wave halves half a step apart (4-slot ring, stage kt + 2
+        // issued in step kt; 136 KiB)
+        else if constexpr (kI4G128) return launch_exact_tile<BITS, YT, 8, 4, 2, 1, EPI, false, 1, 4, 1, true, true>(a, 1, st);
         else return launch_exact_tile<BITS, YT, 8, 4, 2, G64 / 2, EPI>(a, 1, st);
     }
     if constexpr (kI4G128) {
@@ -1205,16 +1078,12 @@ int launch_exact_bits(const ExactGemmArgs &a, hipStream_t st) {
             default: return launch_exact_tile<BITS, YT, 4, 1, 2, 1, EPI, false, 1, kMidRing>(a, 1, st);
             }
         }
-#if DLLM_EXACT_KG2
         if (p.kgroups == 2)
             return p.tile_m == 128 ? launch_exact_tile<BITS, YT, 4, 4, 2, 1, EPI, false, 1, 2, 2>(a, 1, st)
                                    : launch_exact_tile<BITS, YT, 4, 2, 2, 1, EPI, false, 1, 2, 2>(a, 1, st);
-#endif
     }
     if (p.kgroups != 1 || p.tile_n != 128) return fail(DLLM_ERR_UNSUPPORTED, "exact GEMM: no kernel for the plan");
-#if DLLM_EXACT_MR2
     if (p.tile_m == 64) return launch_exact_tile<BITS, YT, 4, 2, 1, G64, EPI>(a, ns, st);
-#endif
     return launch_exact_tile<BITS, YT, 4, 4, 1, G64, EPI>(a, ns, st);
 }
 
@@ -1233,14 +1102,6 @@ int launch_exact_kpg(const ExactGemmArgs &a, int y_f32, hipStream_t st) {
 #if DLLM_STAMP
 DLLM_STAMP_READER(dllm_stamp_read_exact, g_stamp_exact)
 #endif
-
-void select_exact_plan(int bits, int M, int K, int Npad, int group, dllm_linear_plan_t *p) {
-    exact_plan(bits, M, K, Npad, group, p);
-}
-
-bool exact_gemm_supported(int M, int K, int Npad, int group) {
-    return M >= 1 && Npad % 128 == 0 && K % group == 0 && (group == 64 || group == 128 || group == 256);
-}
 
 int launch_exact_gemm(const ExactGemmArgs &a, int y_f32, hipStream_t st) {
     if (!exact_gemm_supported(a.M, a.K, a.Npad, a.group))

@@ -23,25 +23,6 @@
 #include "dllm_quant_lab.h"   // the lab build's extra entry point
 #endif
 
-#ifndef DLLM_LAB
-#define DLLM_LAB 0
-#endif
-// Horner-form exact GEMM: 1 = half of the reps are rescaled in the tail of the group's last stage
-// (the next group's ratios travel with that stage), half at the head of the group's first stage.
-#ifndef DLLM_EXACT_HORNER
-#define DLLM_EXACT_HORNER 0
-#endif
-#ifndef DLLM_HORNER_SPLIT
-#define DLLM_HORNER_SPLIT 0
-#endif
-// Horner form: 1 = the ratios travel only with a group's first stage (one LDS-DMA per two stages).
-#ifndef DLLM_HORNER_HR_GF
-#define DLLM_HORNER_HR_GF 0
-#endif
-#if DLLM_HORNER_HR_GF && DLLM_HORNER_SPLIT
-#error "DLLM_HORNER_SPLIT reads the next group's ratios in every group's second stage"
-#endif
-
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -487,7 +468,7 @@ wq_gemm8_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *__re
     // issue shortens the landing slack before the counted wait two steps on.  HORNER: + the
     // group's ratios (wave 1).
     constexpr int kPieces = SL::kXRounds + 2 + (HORNER ? 1 : 0);
-    auto piece = [&](uint8_t *sb, unsigned kt, int p, bool with_hr) {
+    auto piece = [&](uint8_t *sb, unsigned kt, int p) {
         const uint32_t base = __builtin_amdgcn_readfirstlane(lds_addr(sb));
         kt += kt0;
         if (p < SL::kXRounds) {
@@ -511,19 +492,17 @@ wq_gemm8_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *__re
             }
         } else if (p == SL::kXRounds + 1) {
             if (has_sz) glds16_asm(szsrc + (kt / kpg) * Npad, base + SL::kX + SL::kW);
-        } else if (has_hr && with_hr) {
-            // SPLIT: a group's second stage carries the NEXT group's ratios (row G = 1 after the last)
-            glds16_asm(hrsrc + (kt / kpg + (DLLM_HORNER_SPLIT ? (kt & 1) : 0)) * Npad, base + kHR);
+        } else if (has_hr) {
+            glds16_asm(hrsrc + (kt / kpg) * Npad, base + kHR);
         }
     };
-    // with_hr (DLLM_HORNER_HR_GF): the stage opens a group, so its ratios travel with it
-    auto stage = [&](uint8_t *sb, unsigned kt, bool with_hr = true) {
+    auto stage = [&](uint8_t *sb, unsigned kt) {
 #pragma unroll
-        for (int p = 0; p < kPieces; ++p) piece(sb, kt, p, with_hr);
+        for (int p = 0; p < kPieces; ++p) piece(sb, kt, p);
     };
     // Counted wait leaving the newest stage's DMAs (this wave's own count) in flight.
-    auto wait_prev = [&](bool newest_hr = true) {
-        if (has_w && (has_sz || (has_hr && newest_hr))) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SL::kXRounds + SL::kWOps + 1) : "memory");
+    auto wait_prev = [&]() {
+        if (has_w && (has_sz || has_hr)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SL::kXRounds + SL::kWOps + 1) : "memory");
         else if (has_w) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SL::kXRounds + SL::kWOps) : "memory");
         else if (has_sz) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SL::kXRounds + 1) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SL::kXRounds) : "memory");
@@ -564,7 +543,7 @@ wq_gemm8_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *__re
     auto step = [&](const uint8_t *sb, uint8_t *pf, unsigned kt, auto gf_tag) {
         constexpr bool GF = HORNER && decltype(gf_tag)::value;
         const bool issue = kt + 2 < nk;
-        if (!(LAB & 32) && issue) stage(pf, kt + 2, !DLLM_HORNER_HR_GF || GF);   // kt + 2 has kt's group phase
+        if (!(LAB & 32) && issue) stage(pf, kt + 2);
         if constexpr (LAB & 4) {   // measurement only: the ring and its waits without any compute
             if (issue) wait_prev();
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -587,7 +566,7 @@ wq_gemm8_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *__re
         ExactConsts ec;
         float4 r4[4];
         if constexpr (HORNER) ec = exact_consts(nz);
-        if constexpr (GF || (HORNER && DLLM_HORNER_SPLIT)) {
+        if constexpr (GF) {
             const float *rl = reinterpret_cast<const float *>(sb + kHR) + cw * 32 + 4 * hsel;
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) r4[qd] = *reinterpret_cast<const float4 *>(rl + 8 * qd);
@@ -603,7 +582,6 @@ wq_gemm8_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *__re
             if (issue) stage(pf, kt + 2);
         }
         half8_t aA = deq(0), aB;
-        constexpr int kRH = (HORNER && DLLM_HORNER_SPLIT) ? MR / 2 : MR;   // reps rescaled at the group's head
         auto rescale = [&](int r) {
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) {
@@ -626,28 +604,17 @@ wq_gemm8_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *__re
                 // MFMAs, MI355X_MICROARCH.md filler prices)
 #pragma unroll
                 for (int r = 0; r < MR; ++r) {
-                    if (r < kRH) rescale(r);
+                    rescale(r);
                     acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ac, bc[r], acc[r], 0, 0, 0);
                 }
                 // rep i + 1's rescale issues beside rep i's MFMA (one rep of slack before its use)
                 __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);
 #pragma unroll
                 for (int i = 0; i < MR; ++i) {
-                    if (i + 1 < kRH) __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);
+                    if (i + 1 < MR) __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // MFMA rep i
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, kRH < MR ? 2 : 1, 0);
-                }
-            } else if (HORNER && kRH < MR && !GF && j == kSub - 1) {
-                // the group's last substep: reps kRH.. take the next group's ratio after their last
-                // MFMA of this group (rep r's rescale beside rep r + 2's MFMA)
-                mfma8(ac, bc);
-#pragma unroll
-                for (int r = kRH; r < MR; ++r) rescale(r);
-#pragma unroll
-                for (int i = 0; i < MR; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i >= kRH + 2) __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
                 }
             } else {
                 mfma8(ac, bc);
@@ -668,7 +635,7 @@ wq_gemm8_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *__re
             sub(bB, bA, aB, aA, 3);
         }
         // Stage kt+1 must have landed; kt+2's DMAs may stay in flight across the barrier.
-        if (issue && !(LAB & 16)) wait_prev(!DLLM_HORNER_HR_GF || GF);
+        if (issue && !(LAB & 16)) wait_prev();
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -676,8 +643,8 @@ wq_gemm8_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *__re
     };
 
     stage(st0, 0);
-    if (nk > 1) stage(st1, 1, !DLLM_HORNER_HR_GF || !HORNER);
-    if (nk > 1) wait_prev(!DLLM_HORNER_HR_GF || !HORNER);
+    if (nk > 1) stage(st1, 1);
+    if (nk > 1) wait_prev();
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -813,10 +780,6 @@ wq_gemm8_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *__re
 #include "lab/wq_ring256.inc"
 #endif
 
-#ifndef DLLM_DECODE_XL
-#define DLLM_DECODE_XL 1
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // Decode GEMM (small M, weight-streaming / HBM-bound): one block per 16 NT-column group and
 // K-slice (grid Npad/(16 NT) x nsplit), 8 waves split the block's K-slice by 128-deep slabs,
@@ -830,7 +793,6 @@ wq_gemm8_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *__re
 // word/pair order as the prefill layout with the 32-deep step t in place of the substep.
 // ---------------------------------------------------------------------------------------------
 typedef float float4_t __attribute__((ext_vector_type(4)));
-constexpr int kDecWaves = 8;
 #if DLLM_STAMP
 // phase stamps of wq_decode_kernel (stamp build only): 0 entry, 1 + 2 r / 2 + 2 r round r's loads
 // issued / its MFMAs issued, kEpi the wave partials in LDS, kEnd exit
@@ -1122,26 +1084,7 @@ DLLM_STAMP_READER(dllm_stamp_read_dec, g_stamp_dec)
 namespace {
 #endif
 
-constexpr int kDecodeMaxM = 64;
-
-// XL decode (M <= 16): dynamic LDS of X rows + zero row (2K + 16 B each) + pair and scale rows
-// (256 B per 4 groups each), within the CU's 160 KiB beside the 8 KiB partial-sum buffer.
-constexpr size_t kXlLdsMax = 160 * 1024 - kDecWaves * 64 * 4 * 4;
-inline size_t xl_lds_bytes(int M, int K, int group) {
-    const size_t nq = static_cast<size_t>((K / group + 3) / 4);
-    return static_cast<size_t>(M + 1) * (2 * static_cast<size_t>(K) + 16) + 2 * nq * 256;
-}
-
-// What the kernel selection reads of a layer: a handle's facts (plan_shape_of) or the arguments of
-// dllm_linear_plan_shape.  horner_ok = the create's check of the Horner ratios passed (hstate == 1).
-struct PlanShape {
-    size_t K = 0, N = 0, Npad = 0, group = 0;
-    int bits = 0, precision = DLLM_PRECISION_EXACT;
-    bool horner_ok = false, decode_layout = false;
-#if DLLM_LAB
-    int variant = -1;   // lab A/B: the handle's schedule variant
-#endif
-};
+// A handle's facts for the kernel selection (linear_plan.hpp).
 inline PlanShape plan_shape_of(const dllm_linear *h) {
     PlanShape s;
     s.K = h->K; s.N = h->N; s.Npad = h->Npad; s.group = h->group;
@@ -1152,53 +1095,12 @@ inline PlanShape plan_shape_of(const dllm_linear *h) {
 #endif
     return s;
 }
-
-// Exact-weight kernels apply when the group tiles K (a stage never straddles two groups).
-inline bool use_exact(const PlanShape *h) {
-    return h->precision == DLLM_PRECISION_EXACT &&
-           exact_gemm_supported(1, static_cast<int>(h->K), static_cast<int>(h->Npad), static_cast<int>(h->group));
-}
 inline bool use_exact(const dllm_linear *h) {
     const PlanShape s = plan_shape_of(h);
     return use_exact(&s);
 }
-
-// Decode tile policy: (NT, nsplit) per M bucket, chosen from the M-sweep.
-// Measured (scripts/decode_sweep.py, 48-layer graph, K = N = 4096 int4, us per layer;
-// profiles/r01_decode_tiles): up to M = 32 the one-tile kernel wins (M 1/16/32: 5.1/6.9/10.7;
-// the slab combine's extra launch costs ~4.7 us and NT = 4 without a split leaves 64 blocks whose
-// per-CU load rate bounds the stream); at M 33..64 X re-reads dominate and NT 4 x 4 K-slices
-// wins (M 64: 13.8 vs 18.6).
-inline void decode_policy(int M, int &nt, int &nsplit) {
-    nt = nsplit = M > 32 ? 4 : 1;
-}
-
-// The decode plan for M <= kDecodeMaxM rows: tile_m = the M bucket (16 MT), tile_n = 16 NT, nsplit
-// K slices of whole 128-deep slabs, DLLM_PLAN_DECODE_XL where X is staged in LDS.  nt0 / nsplit0 > 0:
-// the lab build's (NT, nsplit) override in place of decode_policy.
-inline void decode_plan(const PlanShape *h, int M, dllm_linear_plan_t *p, int nt0 = 0, int nsplit0 = 0) {
-    int nt, nsplit;
-    decode_policy(M, nt, nsplit);
-    if (nt0 > 0) { nt = nt0; nsplit = nsplit0; }
-    // the column group must tile Npad (a multiple of 128)
-    while (nt > 1 && h->Npad % (16 * nt)) nt /= 2;
-    const int K = static_cast<int>(h->K), gr = static_cast<int>(h->group);
-    const int nslab = (K + 127) / 128;
-    nsplit = std::max(1, std::min(nsplit, nslab));
-    p->kernel = DLLM_KERNEL_DECODE;
-    p->tile_m = M <= 16 ? 16 : (M <= 32 ? 32 : 64);
-    p->tile_n = 16 * nt;
-    p->kgroups = 1;
-    p->nsplit = nsplit;
-    p->flags = nsplit > 1 ? DLLM_PLAN_SPLITK : 0;
-    // M 9..16 only: M = 16 6.75 vs 7.25 us per layer in the 40-layer chain, M = 1 / 2 / 4 / 8
-    // 5.16 / 5.34 / 5.58 / 6.00 vs 5.18 / 5.38 / 5.47 / 5.94 (profiles/r05_decode_xl/): fewer
-    // load instructions do not shorten the M <= 8 layer, whose time is the weight stream's
-    // latency, and the DMA wait + barrier before the first MFMA costs a little there.
-    if (DLLM_DECODE_XL && nsplit == 1 && nt == 1 && M <= 16 && use_exact(h) && gr != 64 && M > 8 && K % 512 == 0 &&
-        nslab >= kDecWaves && xl_lds_bytes(M, K, gr) <= kXlLdsMax)
-        p->flags |= DLLM_PLAN_DECODE_XL;
-}
+// A failed check of the plan module becomes the C API's error (dllm_last_error).
+inline int fail_if(const PlanError &e) { return e.code ? fail(e.code, e.msg) : DLLM_OK; }
 
 template <int BITS, typename YT, int MT, int NT, int EXACT>
 int launch_decode_nt(const dllm_linear *h, const __half *X, int M, YT *Y, int nsplit, bool xl, hipStream_t st) {
@@ -1206,7 +1108,6 @@ int launch_decode_nt(const dllm_linear *h, const __half *X, int M, YT *Y, int ns
     const int K = static_cast<int>(h->K), N = static_cast<int>(h->N);
     const int Np = static_cast<int>(h->Npad), gr = static_cast<int>(h->group);
     if (nsplit == 1) {
-#if DLLM_DECODE_XL
         if constexpr (MT == 1 && NT == 1 && EXACT == 2) {
             if (xl) {   // DLLM_PLAN_DECODE_XL (decode_plan)
                 const size_t bytes = xl_lds_bytes(M, K, gr);
@@ -1228,7 +1129,6 @@ int launch_decode_nt(const dllm_linear *h, const __half *X, int M, YT *Y, int ns
                 return DLLM_OK;
             }
         }
-#endif
 #if DLLM_LAB
         if constexpr (MT * NT <= 2) {
             if (h->variant == 306) {   // lab A/B: 16 waves per block (two slabs each at K = 4096)
@@ -1364,193 +1264,12 @@ int launch_ring(const dllm_linear *h, const __half *X, int M, YT *Y, hipStream_t
 #include "lab/wq_lab_launch.inc"
 #endif
 
-// Rounded-weight (DLLM_PRECISION_F16W) tile policy: the largest tile that still gives >= 256
-// blocks -- 256 x 256 (8 waves), 256 x 128 (8 waves, two k-groups) -- below that 128 x 128 tiles
-// (two k-groups) with K split until ~200+ blocks (slab partials + ordered combine).
-inline void rounded_plan(const PlanShape *h, int M, dllm_linear_plan_t *p) {
-    const int np = static_cast<int>(h->Npad);
-    const int mb256 = (M + 255) / 256, mb128 = (M + 127) / 128;
-    auto set = [&](int tm, int tn, int kg, int ns) {
-        p->kernel = DLLM_KERNEL_ROUNDED_RING;
-        p->tile_m = tm; p->tile_n = tn; p->kgroups = kg; p->nsplit = ns;
-        p->flags = ns > 1 ? DLLM_PLAN_SPLITK : 0;
-    };
-    if (np % 256 == 0 && mb256 * (np / 256) >= kCUs) return set(256, 256, 1, 1);
-    if (mb256 * (np / 128) >= kCUs) return set(256, 128, 2, 1);
-    const int tiles = mb128 * (np / 128);
-    const int nk = static_cast<int>(h->K / kBK);
-    int nsplit = 1;
-    while (tiles * nsplit < 200 && nsplit < 8 && nk % (2 * nsplit) == 0 && nk / (2 * nsplit) >= 4) nsplit *= 2;
-    return set(128, 128, 2, nsplit);
-}
-
 template <int BITS, typename YT, int EPI = 0>
 int launch_rounded(const dllm_linear *h, const __half *X, int M, YT *Y, hipStream_t st, const dllm_linear_plan_t &p,
                    const PSampleEpi *epi = nullptr) {
     if (p.tile_n == 256) return launch_ring<BITS, YT, 8, 8, 1, EPI>(h, X, M, Y, st, 1, epi);
     if (p.tile_m == 256) return launch_ring<BITS, YT, 4, 8, 2, EPI>(h, X, M, Y, st, 1, epi);
     return launch_ring<BITS, YT, 4, 4, 2, EPI>(h, X, M, Y, st, p.nsplit, epi);
-}
-
-// Exact-weight GEMM in Horner form (wq_gemm8_kernel<..., HORNER>, 256 x 256 tiles): for int4 g128
-// on grids of >= 256 such tiles.  The ratios and their validity are decided once, by the handle's
-// create (finish_linear); a handle whose scales fail the check runs the fold-form exact kernels.
-#if DLLM_LAB
-inline bool lab_horner128() {
-    static const bool on = std::getenv("DLLM_LAB_HORNER128") != nullptr;
-    return on;
-}
-#endif
-
-// int4 and (256 x 256 tiles only: horner_ready) int2 codes, group 128.
-inline bool horner_shape(const PlanShape *h) {
-    return h->precision == DLLM_PRECISION_EXACT && (h->bits == 4 || h->bits == 2) && h->group == 128 &&
-           h->K % 128 == 0 && h->Npad % 256 == 0;
-}
-
-// The handle's Horner ratios are valid (decided at create, immutable afterwards).
-inline bool ensure_horner(const PlanShape *h) { return h->horner_ok; }
-
-// DLLM_POLICY_ROUNDS (product; 0 = the earlier full-round thresholds, A/B): a grid short of a round
-// takes the larger tiles when the alternative needs more rounds -- a 256 x 256 Horner round takes
-// about two 128 x 256 PC rounds, a 128 x 256 PC round about 1.78 two-k-group 128 x 128 rounds
-// (58.6 vs 33 us at K 4096).  N 4096, 40-layer chain (profiles/r06_tiles/policy_rounds_ab.jsonl):
-// M 1100 / 1280 / 1536 / 1800: 63.2 / 61.0 / 62.1 / 68.2 -> 56.8 / 52.3 / 53.2 / 59.0 us (128 x 256
-// PC tiles short of a round), M 2304 / 2560 / 3072 / 3584: 106.5 / 106.7 / 107.7 / 112.6 -> 97.3 /
-// 97.3 / 98.4 / 104.0 us (256 x 256 Horner tiles short of a round), M 2048 and 4096 unchanged.
-#ifndef DLLM_POLICY_ROUNDS
-#define DLLM_POLICY_ROUNDS 1
-#endif
-bool horner_ready(const PlanShape *hc, int M) {
-    const int np = static_cast<int>(hc->Npad);
-    if (!horner_shape(hc)) return false;
-    // rounds of 256 tiles: a 256 x 256 round takes about two 128 x 256 rounds, so the Horner grid
-    // must not need more rounds than half the fold form's (M = 4300: 2 vs 3 rounds -> fold form)
-    const int t256 = ((M + 255) / 256) * (np / 256), t128 = ((M + 127) / 128) * (np / 256);
-#if DLLM_LAB
-    if (hc->variant == 14) return false;   // lab A/B: the fold-form exact policy
-    if (lab_horner128()) {                 // lab A/B: Horner form on 128 x 256 tiles
-        if (t128 < kCUs) return false;
-    } else
-#endif
-    if ((!DLLM_POLICY_ROUNDS && t256 < kCUs) || 2 * ((t256 + kCUs - 1) / kCUs) > (t128 + kCUs - 1) / kCUs)
-        return false;
-    return ensure_horner(hc);
-}
-
-// The Horner kernel on 128-token tiles (wq_horner16_kernel<..., TB = 8>, x 256 columns, 128-deep
-// stages), for grids where the 256 x 256 Horner grid leaves CUs idle but 128 x 256 tiles fill a round
-// (M = 2048 at N = 4096; the 2-GPU column shard, M = 4096 x N 2048).  Lab A/B only (variant 323):
-// against the fold form on those grids it measured -2.8 % on one box and +8 % on another (M = 2048:
-// 64.9 vs 66.7 us, 72.5 vs 67.0 us; profiles/r04_horner/), so the fold form stays the product path.
-// Returns the tile rows, 0 = not applicable.
-#if DLLM_LAB
-int horner_rows(const PlanShape *hc, int M) {
-    const int np = static_cast<int>(hc->Npad);
-    if (hc->variant != 323 || hc->bits != 4 || !horner_shape(hc) || !hc->horner_ok) return 0;
-    if (((M + 127) / 128) * (np / 256) >= kCUs) return 128;
-    return 0;
-}
-#endif
-
-// The KG2 Horner kernel (256 x 128 tiles, two k-groups): where neither the 256 x 256 Horner grid
-// nor the fold form's 128 x 256 grid fills a round but the 256 x 128 grid does (N = 4096: M
-// 1793..1920; measured at M = 1800: 69.2 vs 74.9 us).  At M = 2048 the 128 x 256 fold grid fills
-// the chip and is as fast (68.5 vs 69.6 us: KG2 stages two K-halves' X slices, 72 KiB per k-step
-// against 24 KiB for the same MFMAs; profiles/r03_kg2/).  prefill_plan asks horner_pc_ready first,
-// which since DLLM_POLICY_ROUNDS takes M 1793..1920 at N = 4096 (240 PC tiles against two rounds of
-// 128 x 128): what reaches this kernel now is ceil(M / 128) == ceil(M / 256), i.e. M <= 128, on 256
-// to 510 column tiles of 128 (M = 100, K = 512, N = 32768; tests/test_gpu_linear_kernels.py).
-bool horner_kg2_ready(const PlanShape *hc, int M) {
-    const int np = static_cast<int>(hc->Npad);
-    if (!(hc->precision == DLLM_PRECISION_EXACT && hc->bits == 4 && hc->group == 128 && hc->K % 256 == 0 &&
-          np % 128 == 0 && hc->horner_ok))
-        return false;
-#if DLLM_LAB
-    if (hc->variant == 14 || hc->variant == 28) return false;   // lab A/B: the fold-form exact policy
-#endif
-    const int t256 = ((M + 255) / 256) * (np / 256), tk = ((M + 255) / 256) * (np / 128);
-    const int t128 = ((M + 127) / 128) * (np / 256);
-    return t256 < kCUs && t128 < kCUs && tk >= kCUs;
-}
-
-// The producer / consumer Horner kernel (128 x 256 tiles, linear_pc.hip): where the 256 x 256
-// Horner grid does not fill a round and the 128 x 256 grid does (N = 4096: M 1921..4096 minus the
-// Horner grid's own range; M = 2048 = config C2 and the C5 layers; the 2-GPU column shard).
-#ifndef DLLM_HORNER_PC
-#define DLLM_HORNER_PC 1
-#endif
-bool horner_pc_ready(const PlanShape *hc, int M) {
-#if DLLM_HORNER_PC
-    const int np = static_cast<int>(hc->Npad);
-    if (hc->bits != 4 || !horner_shape(hc) || !hc->horner_ok) return false;
-#if DLLM_LAB
-    if (hc->variant == 14 || hc->variant == 28) return false;   // lab A/B: the fold-form exact policy
-#endif
-    const int t128 = ((M + 127) / 128) * (np / 256);
-    if (horner_ready(hc, M)) return false;
-    if (t128 >= kCUs) return true;
-    if (!DLLM_POLICY_ROUNDS || np % 128 != 0 || hc->K % 256 != 0) return false;
-    const int tk = ((M + 127) / 128) * (np / 128);   // the two-k-group 128 x 128 grid
-    return 178 * ((t128 + kCUs - 1) / kCUs) <= 100 * ((tk + kCUs - 1) / kCUs);
-#else
-    (void)hc; (void)M;
-    return false;
-#endif
-}
-
-// The two-k-group PC kernel (rows x 128 tiles, linear_pc.hip): where none of the larger Horner grids
-// fills a round, 128- or 64-row tiles by rounds x tile time (below) (128: the 4-GPU
-// column shard M = 4096 x N 1024, M = 2048 x N 2048, M = 1024 x N 4096: 34.8 -> 32.3 us; 64: M = 512
-// x N 4096 and the 8-GPU shard 4096 x 512: 22.1 -> 21.5 us).  32-row tiles (DLLM_PC_KG2_SMALL, A/B)
-// lose to the 4-k-group fold tiles at mid M (M 256: 17.1 vs 14.3 us; profiles/r06_tiles/).  Returns
-// the tile rows, 0 = not applicable.
-#ifndef DLLM_HORNER_PC_KG2
-#define DLLM_HORNER_PC_KG2 1
-#endif
-// A 64-row grid of at least 3/4 of a round takes the two-k-group PC kernel: M 321..448 at N 4096
-// (192..224 tiles) ran 21.3 / 21.4 us at M 384 / 448 against 21.8 / 23.4 for the 4-k-group fold
-// tiles of mid M; at 5/8 of a round (M 300, 160 tiles) the fold tiles stay faster (21.4 vs 22.8 us;
-// profiles/r06_tiles/pc_kg2_fill_ab.jsonl, 40-layer chain).
-#ifndef DLLM_PC_KG2_MINFILL
-#define DLLM_PC_KG2_MINFILL (3 * kCUs / 4)
-#endif
-#ifndef DLLM_PC_KG2_SMALL   // 64- and 32-token tiles too
-#define DLLM_PC_KG2_SMALL 0
-#endif
-int horner_pc_kg2_rows(const PlanShape *hc, int M) {
-#if DLLM_HORNER_PC_KG2
-    const int np = static_cast<int>(hc->Npad);
-    if (!(hc->precision == DLLM_PRECISION_EXACT && hc->bits == 4 && hc->group == 128 && hc->K % 256 == 0 &&
-          np % 128 == 0 && hc->horner_ok))
-        return 0;
-#if DLLM_LAB
-    if (hc->variant == 14 || hc->variant == 28) return 0;   // lab A/B: the fold-form exact policy
-#endif
-    if (horner_ready(hc, M) || horner_pc_ready(hc, M) || horner_kg2_ready(hc, M)) return 0;
-#if DLLM_PC_KG2_SMALL
-    for (int rows = 128; rows >= 32; rows /= 2) {
-        const int t = ((M + rows - 1) / rows) * (np / 128);
-        if (t >= 2 * kCUs) return 0;
-        if (t >= DLLM_PC_KG2_MINFILL) return rows;
-    }
-    return 0;
-#else
-    // A 128-row tile takes ~1.55x a 64-row one (33 vs 21 us at K 4096: the 4- and 8-GPU shards), so
-    // a grid of 128-row tiles short of a round still beats two rounds of 64-row tiles, and a single
-    // round of 64-row tiles beats one of 128-row tiles.  N 4096: M 513..768 now take 128-row tiles
-    // (M 700 / 768: 42.1 / 39.1 -> 33.3 / 30.5 us in the 40-layer chain; they took 64-row tiles in
-    // 1.1 - 1.5 rounds) and M 321..448 64-row tiles (a 64-row grid of fewer than
-    // DLLM_PC_KG2_MINFILL tiles leaves mid M to the fold tiles); profiles/r06_tiles/pc_kg2_fill_ab.jsonl, pc_kg2_policy_ab.jsonl.
-    const int t128 = ((M + 127) / 128) * (np / 128), t64 = ((M + 63) / 64) * (np / 128);
-    if (t128 >= 2 * kCUs) return 0;   // the larger tiles of the other kernels fill the chip
-    if (t128 >= kCUs || t64 > kCUs) return 128;
-    return t64 >= DLLM_PC_KG2_MINFILL ? 64 : 0;
-#endif
-#else
-    (void)hc; (void)M;
-    return 0;
-#endif
 }
 
 template <typename YT, int EPI>
@@ -1598,33 +1317,6 @@ inline ExactGemmArgs exact_args(const dllm_linear *h, const __half *X, int M, vo
     return a;
 }
 
-// The one kernel selection of the linear layer: dllm_linear_plan(_shape) report it and the launchers
-// below switch on it.  Prefill (M > kDecodeMaxM, or no decode layout): the exact-weight kernels
-// (default precision) -- the Horner family where its grids fit, else the fold-form tiles
-// (select_exact_plan) -- or the rounded ring.
-inline void prefill_plan(const PlanShape *h, int M, dllm_linear_plan_t *p) {
-    if (!use_exact(h)) return rounded_plan(h, M, p);
-    auto horner = [&](int kernel, int tm, int tn, int kg) {
-        p->kernel = kernel;
-        p->tile_m = tm; p->tile_n = tn; p->kgroups = kg; p->nsplit = 1;
-        p->flags = 0;
-    };
-    if ((h->bits == 4 || h->bits == 2) && horner_ready(h, M)) return horner(DLLM_KERNEL_HORNER16, 256, 256, 1);
-    if (h->bits == 4 && horner_pc_ready(h, M)) return horner(DLLM_KERNEL_HORNER_PC, 128, 256, 1);
-    if (h->bits == 4 && horner_kg2_ready(h, M)) return horner(DLLM_KERNEL_HORNER_KG2, 256, 128, 2);
-    if (const int rows = h->bits == 4 ? horner_pc_kg2_rows(h, M) : 0)
-        return horner(DLLM_KERNEL_HORNER_PC_KG2, rows, 128, 2);
-    select_exact_plan(h->bits, M, static_cast<int>(h->K), static_cast<int>(h->Npad), static_cast<int>(h->group), p);
-}
-
-// `fused`: the plan of dllm_linear_forward_psample(_ex), whose M <= kDecodeMaxM calls run the plain
-// GEMM and the p_sample kernel.
-inline void select_plan(const PlanShape *h, size_t M, int fused, dllm_linear_plan_t *p) {
-    if (M <= static_cast<size_t>(kDecodeMaxM) && h->decode_layout) decode_plan(h, static_cast<int>(M), p);
-    else prefill_plan(h, static_cast<int>(M), p);
-    if (fused && M <= static_cast<size_t>(kDecodeMaxM)) p->flags |= DLLM_PLAN_NOT_FUSED;
-}
-
 template <int BITS, typename YT, int EPI = 0>
 int launch_prefill_auto(const dllm_linear *h, const __half *X, int M, YT *Y, hipStream_t st,
                         const dllm_linear_plan_t &p, const PSampleEpi *epi = nullptr) {
@@ -1665,11 +1357,7 @@ int launch_prefill_auto(const dllm_linear *h, const __half *X, int M, YT *Y, hip
         if (const int rows = BITS == 4 ? horner_rows(&s, M) : 0)   // lab A/B 323 only
             return launch_horner_rows_gemm(ha, rows, y_f32, st);
 #endif
-        ExactGemmArgs a = exact_args(h, X, M, Y, epi);
-#if DLLM_EXACT_HORNER   // A/B build: the 128 x 256 exact tiles in Horner form too
-        if (BITS == 4 && h->hstate == 1) a.hr = h->hr;
-#endif
-        return launch_exact_gemm(a, y_f32, st);
+        return launch_exact_gemm(exact_args(h, X, M, Y, epi), y_f32, st);
     }
     case DLLM_KERNEL_ROUNDED_RING: return launch_rounded<BITS, YT, EPI>(h, X, M, Y, st, p, epi);
     default: break;
@@ -1710,19 +1398,6 @@ void free_linear(dllm_linear *h) {
     (void)hipFree(h->w16);
 #endif
     delete h;
-}
-
-int check_shape(size_t K, size_t N, uint8_t bits, size_t group, int flags) {
-    const int precision = flags & ~DLLM_LINEAR_PREFILL_ONLY;
-    if (bits != 2 && bits != 4 && bits != 8)
-        return fail(DLLM_ERR_UNSUPPORTED, "linear layer supports bits in {2, 4, 8}");
-    if (K == 0 || N == 0) return fail(DLLM_ERR_SHAPE_MISMATCH, "K and N must be >= 1");
-    if (K % kBK) return fail(DLLM_ERR_SHAPE_MISMATCH, "K must be a multiple of 64");
-    if (group == 0 || group % kBK) return fail(DLLM_ERR_INVALID_PARAMS, "group must be a positive multiple of 64");
-    if (K > (1u << 30) || N > (1u << 30)) return fail(DLLM_ERR_SHAPE_MISMATCH, "dimension too large");
-    if (precision != DLLM_PRECISION_EXACT && precision != DLLM_PRECISION_F16W)
-        return fail(DLLM_ERR_INVALID_PARAMS, "precision must be DLLM_PRECISION_EXACT or DLLM_PRECISION_F16W");
-    return DLLM_OK;
 }
 
 int alloc_linear(size_t K, size_t N, uint8_t bits, size_t group, int flags, dllm_linear **out) {
@@ -1833,7 +1508,7 @@ extern "C" {
 int dllm_linear_create_ex(const float *W, const float *bias, size_t K, size_t N, uint8_t bits, size_t group,
                           int precision, dllm_linear_t *out, dllm_stream_t stream) {
     if (!out || !W) return fail(DLLM_ERR_INVALID_PARAMS, "null pointer");
-    int rc = check_shape(K, N, bits, group, precision);
+    int rc = fail_if(check_shape(K, N, bits, group, precision));
     if (rc) return rc;
     dllm_linear *h = nullptr;
     if ((rc = alloc_linear(K, N, bits, group, precision, &h))) return rc;
@@ -1870,7 +1545,7 @@ int dllm_linear_create_quantized_ex(const uint8_t *packed_codes, const float *sc
                                     const float *bias, size_t K, size_t N, uint8_t bits, size_t group, int precision,
                                     dllm_linear_t *out, dllm_stream_t stream) {
     if (!out || !packed_codes || !scales || !zps) return fail(DLLM_ERR_INVALID_PARAMS, "null pointer");
-    int rc = check_shape(K, N, bits, group, precision);
+    int rc = fail_if(check_shape(K, N, bits, group, precision));
     if (rc) return rc;
     dllm_linear *h = nullptr;
     if ((rc = alloc_linear(K, N, bits, group, precision, &h))) return rc;
@@ -2051,8 +1726,7 @@ int dllm_linear_info(dllm_linear_t h, size_t *K, size_t *N, uint8_t *bits, size_
 
 int dllm_linear_plan(dllm_linear_t h, size_t M, int fused, dllm_linear_plan_t *out) {
     if (!h || !out) return fail(DLLM_ERR_INVALID_PARAMS, "null argument");
-    if (M == 0 || M > (1u << 30)) return fail(DLLM_ERR_SHAPE_MISMATCH, "M must be 1..2^30");
-    if (fused && h->N % 4) return fail(DLLM_ERR_UNSUPPORTED, "fused p_sample needs N % 4 == 0");
+    if (const int rc = fail_if(check_plan_args(h->N, M, fused))) return rc;
     const PlanShape s = plan_shape_of(h);
     select_plan(&s, M, fused, out);
     return DLLM_OK;
@@ -2061,15 +1735,9 @@ int dllm_linear_plan(dllm_linear_t h, size_t M, int fused, dllm_linear_plan_t *o
 int dllm_linear_plan_shape(size_t K, size_t N, uint8_t bits, size_t group, int flags, int horner_ok, size_t M,
                            int fused, dllm_linear_plan_t *out) {
     if (!out) return fail(DLLM_ERR_INVALID_PARAMS, "null argument");
-    if (const int rc = check_shape(K, N, bits, group, flags)) return rc;
-    if (M == 0 || M > (1u << 30)) return fail(DLLM_ERR_SHAPE_MISMATCH, "M must be 1..2^30");
-    if (fused && N % 4) return fail(DLLM_ERR_UNSUPPORTED, "fused p_sample needs N % 4 == 0");
-    PlanShape s;
-    s.K = K; s.N = N; s.Npad = (N + kBN - 1) / kBN * kBN; s.group = group;
-    s.bits = bits; s.precision = flags & ~DLLM_LINEAR_PREFILL_ONLY;
-    s.decode_layout = (flags & DLLM_LINEAR_PREFILL_ONLY) == 0;
-    // a handle's ratios exist (and can pass the check) only for the Horner-form shapes
-    s.horner_ok = horner_ok != 0 && horner_shape(&s);
+    if (const int rc = fail_if(check_shape(K, N, bits, group, flags))) return rc;
+    if (const int rc = fail_if(check_plan_args(N, M, fused))) return rc;
+    const PlanShape s = plan_shape_for(K, N, bits, group, flags, horner_ok);
     select_plan(&s, M, fused, out);
     return DLLM_OK;
 }
