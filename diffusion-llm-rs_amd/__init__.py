@@ -16,11 +16,13 @@ this package is the host-side mirror of the reference's Rust operator surface:
 * ``diffusion``    -- ``diffuse_llm``'s schedules, add_noise / p_sample (seeded device noise), the
   p_losses objective (per-sample noise MSE in a pinned summation order), the phase-aware
   KVCacheEntry and the denoise loop (last layer fused with p_sample).
+* ``search``       -- exact cosine top-k over the compressed-vector store, scanned on its byte codes
+  (``FusionANN::search`` over ``KVCache``'s records): search_vectors, VectorIndex.
 """
 from . import _lib
 from ._lib import (CalibrationRequired, HipError, InvalidParams, QuantizationError, SerializationError,
                    ShapeMismatch, UnsupportedOperation)
-from . import quantization, quant, kvquant, linear, parallel, diffusion, serde
+from . import quantization, quant, kvquant, linear, parallel, diffusion, serde, search
 from .quantization import (AdaptiveQuantizer, QuantizedKVCacheEntry, QuantizedTensor, compression_ratio, dequantize_tensor, kv_attention,
                            pack, quantize_tensor, quantize_tensor_pair, unpack)
 from .quant import CalibrationData, DefaultQuantizer, QuantizationParams, QuantizationType, quant_utils
@@ -29,6 +31,7 @@ from .linear import MixedPrecisionStack, QuantLinear
 from .diffusion import (AlphaMode, BetaSchedule, Cumprod, DenoiseLoop, DiffusionConfig, KVCacheEntry, KVCacheStore,
                         add_noise, noise_mse, p_losses, p_losses_coeffs,
                         p_sample, randn)
+from .search import VectorIndex, search_table, search_vectors
 
 __all__ = [
     "quantize_tensor", "quantize_tensor_pair", "dequantize_tensor", "pack", "unpack", "compression_ratio", "QuantizedTensor",
@@ -37,7 +40,7 @@ __all__ = [
     "QuantLinear", "MixedPrecisionStack", "QuantizationError", "InvalidParams", "UnsupportedOperation",
     "ShapeMismatch", "CalibrationRequired", "HipError", "BetaSchedule", "Cumprod", "AlphaMode", "DiffusionConfig",
     "KVCacheEntry", "KVCacheStore", "DenoiseLoop", "add_noise", "p_sample", "randn", "AdaptiveQuantizer",
-    "noise_mse", "p_losses", "p_losses_coeffs",
+    "noise_mse", "p_losses", "p_losses_coeffs", "search_vectors", "search_table", "VectorIndex",
 ]
 
 

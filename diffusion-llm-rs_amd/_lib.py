@@ -156,6 +156,11 @@ SIGNATURES = {
     "dllm_noise_mse_workspace": (S, [S, S]),
     "dllm_noise_mse": (INT, [P, INT, P, S, S, U64, U64, P, P, S, P]),
     "dllm_p_losses_host": (INT, [P, P, S, P, P, P, U64, U64, S, S, P]),
+    "dllm_search_workspace": (S, [S, S, S]),
+    "dllm_search_table": (INT, [P, S, S, P, P, P, P]),
+    "dllm_search_vectors": (INT, [P, S, P, P, S, S, S, P, P, P, S, P]),
+    "dllm_search_table_host": (INT, [P, S, S, P, P, P]),
+    "dllm_search_vectors_host": (INT, [P, S, P, P, S, S, S, P, P]),
     "dllm_quantize_tensor_host": (INT, [P, S, U8, P, P, P]),
     "dllm_dequantize_tensor_host": (INT, [P, S, FL, FL, P]),
     "dllm_default_quantize_host": (INT, [P, S, INT, FL, I32, P]),

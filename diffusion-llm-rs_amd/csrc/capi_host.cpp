@@ -3,7 +3,11 @@
 // own stream, runs the same HIP kernels as the device entry points, and synchronises.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <functional>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -57,6 +61,46 @@ struct Staging {
         return DLLM_OK;
     }
 };
+
+// ---- the search rule in plain C++ (include/dllm_quant.h 8g; csrc/search.hip is the device form) ----
+
+// Strand sum of x[d] * y[d]: element d to strand (d / 4) % 64, each strand from +0 over its d
+// ascending with one fmaf per element, the 64 partials by the tree a[i] = a[i] + a[i ^ m].
+// y: the codes (as float), x itself (y_self), or 1.0f when both are null.
+float strand_sum(const float *x, const uint8_t *codes, bool y_self, size_t dim) {
+    float a[64], b[64];
+    for (int i = 0; i < 64; ++i) a[i] = 0.0f;
+    for (size_t d = 0; d < dim; ++d) {
+        const float y = codes ? static_cast<float>(codes[d]) : (y_self ? x[d] : 1.0f);
+        float &acc = a[(d / 4) % 64];
+        acc = std::fmaf(x[d], y, acc);
+    }
+    for (int m = 32; m > 0; m >>= 1) {
+        for (int i = 0; i < 64; ++i) b[i] = a[i] + a[i ^ m];
+        std::memcpy(a, b, sizeof(a));
+    }
+    return a[0];
+}
+
+uint64_t search_key(float s, uint32_t idx) {
+    uint32_t b;
+    std::memcpy(&b, &s, 4);
+    uint32_t ord;
+    if (s != s) {
+        ord = 0u;
+    } else {
+        if (b == 0x80000000u) b = 0u;
+        ord = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    }
+    return (static_cast<uint64_t>(ord) << 32) | static_cast<uint32_t>(~idx);
+}
+
+int search_shape_ok(size_t rows, size_t dim) {
+    if (dim == 0 || dim > 65535) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "dim must be between 1 and 65535");
+    if (rows >= (size_t(1) << 31))
+        return dllm::fail(DLLM_ERR_SHAPE_MISMATCH, "rows must be below 2^31 (the index is an int32)");
+    return DLLM_OK;
+}
 
 #define STAGE_OK(s) \
     do {            \
@@ -209,6 +253,58 @@ int dllm_p_losses_host(dllm_linear_t h, const float *betas, size_t T, const floa
     if ((rc = dllm_linear_forward(h, dnoisy, B, DLLM_F32, deps, DLLM_F32, s.st))) return rc;
     if ((rc = dllm_noise_mse(deps, DLLM_F32, dn, B, D, seed, offset, dloss, ws, wsb, s.st))) return rc;
     if ((rc = s.download(loss, dloss, B)) || (rc = s.sync())) return rc;
+    return DLLM_OK;
+}
+
+int dllm_search_table_host(const uint8_t *codes, size_t rows, size_t dim, const float *scales, const float *zps,
+                           float *table) {
+    if (int rc = search_shape_ok(rows, dim)) return rc;
+    if (rows == 0) return DLLM_OK;
+    if (!codes || !scales || !zps || !table) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    for (size_t r = 0; r < rows; ++r) {
+        uint32_t c1 = 0, c2 = 0;
+        for (size_t d = 0; d < dim; ++d) {
+            const uint32_t c = codes[r * dim + d];
+            c1 += c;
+            c2 += c * c;
+        }
+        const double s = scales[r], z = zps[r];
+        const double nb2 = ((s * s) * static_cast<double>(c2) + ((2.0 * s) * z) * static_cast<double>(c1)) +
+                           (z * z) * static_cast<double>(dim);
+        const float w = nb2 > 0.0 ? static_cast<float>(1.0 / std::sqrt(nb2)) : 0.0f;
+        table[2 * r] = scales[r] * w;
+        table[2 * r + 1] = zps[r] * w;
+    }
+    return DLLM_OK;
+}
+
+int dllm_search_vectors_host(const float *Q, size_t nq, const uint8_t *codes, const float *table, size_t rows,
+                             size_t dim, size_t k, int32_t *idx, float *scores) {
+    if (k == 0 || k > 256) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "k must be between 1 and 256");
+    if (int rc = search_shape_ok(rows, dim)) return rc;
+    if (nq == 0) return DLLM_OK;
+    if (!Q || !idx || !scores || (rows && (!codes || !table)))
+        return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    std::vector<float> sc(rows);
+    std::vector<uint64_t> keys(rows);
+    const size_t top = std::min(k, rows);
+    for (size_t j = 0; j < nq; ++j) {
+        const float *q = Q + j * dim;
+        const float qs = strand_sum(q, nullptr, false, dim), qn = strand_sum(q, nullptr, true, dim);
+        const float wq = qn > 0.0f ? 1.0f / std::sqrt(qn) : 0.0f;
+        for (size_t r = 0; r < rows; ++r) {
+            const float A = strand_sum(q, codes + r * dim, false, dim);
+            const float vq = table[2 * r + 1] * qs;
+            sc[r] = std::fmaf(table[2 * r], A, vq) * wq;
+            keys[r] = search_key(sc[r], static_cast<uint32_t>(r));
+        }
+        std::partial_sort(keys.begin(), keys.begin() + top, keys.end(), std::greater<uint64_t>());
+        for (size_t i = 0; i < k; ++i) {
+            const uint32_t id = i < top ? ~static_cast<uint32_t>(keys[i]) : 0u;
+            idx[j * k + i] = i < top ? static_cast<int32_t>(id) : -1;
+            scores[j * k + i] = i < top ? sc[id] : -std::numeric_limits<float>::infinity();
+        }
+    }
     return DLLM_OK;
 }
 

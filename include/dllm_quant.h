@@ -509,6 +509,58 @@ size_t dllm_noise_mse_workspace(size_t B, size_t n);
 int dllm_noise_mse(const void *pred, int pred_dtype, const float *noise, size_t B, size_t n, uint64_t seed,
                    uint64_t offset, float *loss, void *workspace, size_t workspace_bytes, dllm_stream_t stream);
 
+/* ---- 8g search: exact cosine top-k over the CompressedVector store, on the byte codes -----------
+ * FusionANN::search (diffusion_prefill/src/fusion_ann.rs:109-136: cosine similarity, sort descending,
+ * take k; "In a real implementation, this would use the quantized index") over what
+ * dllm_compress_vectors emits: codes u8 [rows][dim] (one byte per code whatever `bits` was), scales
+ * f32 [rows], zps f32 [rows].  Brute force and exact; the row is never dequantized.  With
+ * v_d = s c_d + z:  q.v = s sum q_d c_d + z sum q_d,  |v|^2 = s^2 sum c^2 + 2 s z sum c + dim z^2.
+ *
+ * The score rule (the contract: score[j][r] depends on query j and row r alone -- not on nq, rows,
+ * k, the row's place in the store, the grid or the device; a slice of a store gives the same bits).
+ *   Strand sums.  Element d belongs to strand (d / 4) mod 64.  A strand's partial starts at +0 and
+ *   runs over its d ascending with a = fmaf(x_d, y_d, a) (one rounding per element); the 64 partials
+ *   combine by the balanced tree a[i] = a[i] + a[i ^ m], m = 32, 16, 8, 4, 2, 1 (an empty strand is
+ *   +0).  A_jr = strand sum of q_j[d] float(c_r[d]);  Qs_j of q_j[d] 1.0f;  Qn_j of q_j[d] q_j[d].
+ *   Row table (dllm_search_table; once per store).  C1 = sum c, C2 = sum c^2: exact u32 (dim <=
+ *   65535).  In f64, separate IEEE multiplies and adds, s and z widened exactly:
+ *   nb2 = ((s s) C2 + ((2 s) z) C1) + (z z) dim;  w = nb2 > 0 ? (float)(1.0 / sqrt(nb2)) : 0;
+ *   table[r] = {u, v} = {RN(s w), RN(z w)} (f32 multiplies).
+ *   Per query.  wq_j = Qn_j > 0 ? 1.0f / sqrtf(Qn_j) : 0 (correctly rounded f32 sqrt and divide).
+ *   Score.  score_jr = RN(fmaf(u_r, A_jr, RN(v_r Qs_j)) wq_j).  A zero-norm query or row scores 0
+ *   (fusion_ann.rs:131-135).
+ *   Ranking.  By the key (score descending, row index ascending); -0 equals +0; a NaN score ranks
+ *   below -inf.  Keys are unique, so the result is independent of the selection algorithm (the
+ *   reference's order among ties is DashMap iteration order).  When k > rows the tail of the output
+ *   is index -1, score -inf.  The scores returned are the score bits (a -0 stays -0).
+ * Error bound.  For finite inputs without overflow or underflow, against the exact cosine of q_j and
+ * the row as dllm_decompress_vectors returns it (f32 RN(RN(c s) + z)), with T = ceil(dim / 256) and
+ * the cancellation ratio kappa_r = (|s| |c|_2 + |z| sqrt(dim)) / |v|_2 >= 1, to first order
+ *   |score - cos| <= (6 T + 20) 2^-24 kappa_r + 2^-51 kappa_r^3
+ * (a strand chain is 4 T fmafs + 6 tree levels: (4 T + 6) on A and Qs, 4 more on u, v, RN(v Qs) and
+ * the fmaf, all relative to kappa_r |q|; (2 T + 5) + 1 on wq and the last multiply; 4 kappa_r for the
+ * two roundings of each decompressed element; 2^-51 kappa^3 for the f64 cancellation inside nb2). */
+/* Bytes of device workspace dllm_search_vectors needs: the score matrix f32 [nq][rows], two floats
+ * per query and the select passes' candidate keys. */
+size_t dllm_search_workspace(size_t nq, size_t rows, size_t k);
+/* table (device f32 [rows][2]) = {u, v} of every row; one read of the codes.  dim == 0 or > 65535 ->
+ * INVALID_PARAMS; rows >= 2^31 -> SHAPE_MISMATCH; rows == 0 -> DLLM_OK; a NULL pointer ->
+ * INVALID_PARAMS.  Rebuild only the rows that change (pass their slice).  Asynchronous on `stream`. */
+int dllm_search_table(const uint8_t *codes, size_t rows, size_t dim, const float *scales, const float *zps,
+                      float *table /* [rows][2] */, dllm_stream_t stream);
+/* idx (device i32 [nq][k]) and scores (device f32 [nq][k]): the k best rows of each query of Q
+ * (device f32 [nq][dim]) in rank order.  Any dim in 1..65535 and any alignment of codes and Q give
+ * the same bits; dim % 4 == 0 with codes 4-byte and Q 16-byte aligned is the fast path.  Checked in
+ * this order, before anything touches the device: k == 0 or k > 256 -> INVALID_PARAMS; dim == 0 or
+ * > 65535 -> INVALID_PARAMS; rows >= 2^31 -> SHAPE_MISMATCH; nq == 0 -> DLLM_OK, nothing written; a
+ * NULL Q, idx or scores (codes or table with rows > 0) -> INVALID_PARAMS; rows == 0 -> DLLM_OK, the
+ * outputs filled with -1 / -inf; workspace NULL, not 16-byte aligned or shorter than
+ * dllm_search_workspace(nq, rows, k) -> INVALID_PARAMS.  Asynchronous on `stream`; never
+ * synchronises or allocates (graph-capturable from the first call); no atomics. */
+int dllm_search_vectors(const float *Q, size_t nq, const uint8_t *codes, const float *table, size_t rows, size_t dim,
+                        size_t k, int32_t *idx /* [nq][k] */, float *scores /* [nq][k] */,
+                        void *workspace, size_t workspace_bytes, dllm_stream_t stream);
+
 /* ---- host-slice variants (synchronous; stage through device memory; not graph-capturable) ----
  * The literal shapes of the reference's Rust signatures, for callers holding host slices. */
 /* quantize_tensor(&[f32], u8) -> (Vec<u8>, f32, f32): codes one per byte (quantization.rs:38-68). */
@@ -534,6 +586,12 @@ int dllm_linear_forward_host(dllm_linear_t h, const float *X, size_t M, float *Y
  * out), dllm_noise_mse. */
 int dllm_p_losses_host(dllm_linear_t model, const float *betas, size_t T, const float *x_start, const size_t *t,
                        const float *noise, uint64_t seed, uint64_t offset, size_t B, size_t D, float *loss);
+/* dllm_search_table / dllm_search_vectors on host slices: the rule of section 8g in plain C++ (no
+ * device, no staging, no workspace), the same bits as the kernels; the same checks and codes. */
+int dllm_search_table_host(const uint8_t *codes, size_t rows, size_t dim, const float *scales, const float *zps,
+                           float *table /* [rows][2] */);
+int dllm_search_vectors_host(const float *Q, size_t nq, const uint8_t *codes, const float *table, size_t rows,
+                             size_t dim, size_t k, int32_t *idx /* [nq][k] */, float *scores /* [nq][k] */);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@
 // InvalidParams).  Everything here takes and returns host containers, like the Rust APIs.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <optional>
@@ -354,6 +355,27 @@ inline CompressedVector compress_vector(const std::string &id, const std::vector
 // :124-132
 inline std::vector<float> decompress_vector(const CompressedVector &v) {
     return prefill_kvquant_rs::kvquant::BitQuantizer(v.quant_scale, v.quant_zero_point).dequantize(v.data, v.bits);
+}
+// FusionANN::search (fusion_ann.rs:109-136) over stored CompressedVectors of one length: the ids and
+// cosine scores of the k nearest, by dllm_quant.h 8g's rule on the byte codes (host form).
+inline std::vector<std::pair<std::string, float>> search(const std::vector<CompressedVector> &store,
+                                                         const std::vector<float> &query, size_t k) {
+    const size_t rows = store.size(), dim = query.size();
+    std::vector<uint8_t> codes(rows * dim);
+    std::vector<float> scales(rows), zps(rows), table(2 * rows), scores(k);
+    std::vector<int32_t> idx(k);
+    for (size_t r = 0; r < rows; ++r) {
+        if (store[r].data.size() != dim) throw QuantizationError(DLLM_ERR_SHAPE_MISMATCH, "stored vector length != query length");
+        std::copy(store[r].data.begin(), store[r].data.end(), codes.begin() + r * dim);
+        scales[r] = store[r].quant_scale;
+        zps[r] = store[r].quant_zero_point;
+    }
+    detail::check(dllm_search_table_host(codes.data(), rows, dim, scales.data(), zps.data(), table.data()));
+    detail::check(dllm_search_vectors_host(query.data(), 1, codes.data(), table.data(), rows, dim, k, idx.data(),
+                                           scores.data()));
+    std::vector<std::pair<std::string, float>> out;
+    for (size_t i = 0; i < k && idx[i] >= 0; ++i) out.emplace_back(store[idx[i]].id, scores[i]);
+    return out;
 }
 }  // namespace diffusion_prefill
 
