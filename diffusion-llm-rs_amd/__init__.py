@@ -18,11 +18,14 @@ this package is the host-side mirror of the reference's Rust operator surface:
   KVCacheEntry and the denoise loop (last layer fused with p_sample).
 * ``search``       -- exact cosine top-k over the compressed-vector store, scanned on its byte codes
   (``FusionANN::search`` over ``KVCache``'s records): search_vectors, VectorIndex.
+* ``decode``       -- the token readout (``DiffusionPrefill``'s predict / ``sample_token`` step): greedy
+  tokens, {max, softmax denominator} and probabilities of logits [M, vocab] in a pinned,
+  bit-reproducible rule: token_readout, TokenHead.
 """
 from . import _lib
 from ._lib import (CalibrationRequired, HipError, InvalidParams, QuantizationError, SerializationError,
                    ShapeMismatch, UnsupportedOperation)
-from . import quantization, quant, kvquant, linear, parallel, diffusion, serde, search
+from . import quantization, quant, kvquant, linear, parallel, diffusion, serde, search, decode
 from .quantization import (AdaptiveQuantizer, QuantizedKVCacheEntry, QuantizedTensor, compression_ratio, dequantize_tensor, kv_attention,
                            pack, quantize_tensor, quantize_tensor_pair, unpack)
 from .quant import CalibrationData, DefaultQuantizer, QuantizationParams, QuantizationType, quant_utils
@@ -32,6 +35,7 @@ from .diffusion import (AlphaMode, BetaSchedule, Cumprod, DenoiseLoop, Diffusion
                         add_noise, noise_mse, p_losses, p_losses_coeffs,
                         p_sample, randn)
 from .search import VectorIndex, search_table, search_vectors
+from .decode import TokenHead, token_readout
 
 __all__ = [
     "quantize_tensor", "quantize_tensor_pair", "dequantize_tensor", "pack", "unpack", "compression_ratio", "QuantizedTensor",
@@ -41,6 +45,7 @@ __all__ = [
     "ShapeMismatch", "CalibrationRequired", "HipError", "BetaSchedule", "Cumprod", "AlphaMode", "DiffusionConfig",
     "KVCacheEntry", "KVCacheStore", "DenoiseLoop", "add_noise", "p_sample", "randn", "AdaptiveQuantizer",
     "noise_mse", "p_losses", "p_losses_coeffs", "search_vectors", "search_table", "VectorIndex",
+    "token_readout", "TokenHead",
 ]
 
 

@@ -161,6 +161,9 @@ SIGNATURES = {
     "dllm_search_vectors": (INT, [P, S, P, P, S, S, S, P, P, P, S, P]),
     "dllm_search_table_host": (INT, [P, S, S, P, P, P]),
     "dllm_search_vectors_host": (INT, [P, S, P, P, S, S, S, P, P]),
+    "dllm_token_readout_workspace": (S, [S, S]),
+    "dllm_token_readout": (INT, [P, INT, S, S, S, P, P, P, P, S, P]),
+    "dllm_token_readout_host": (INT, [P, INT, S, S, S, P, P, P]),
     "dllm_quantize_tensor_host": (INT, [P, S, U8, P, P, P]),
     "dllm_dequantize_tensor_host": (INT, [P, S, FL, FL, P]),
     "dllm_default_quantize_host": (INT, [P, S, INT, FL, I32, P]),

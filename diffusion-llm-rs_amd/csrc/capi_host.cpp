@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "dllm_quant.h"
+#include "token_exp.hpp"
 
 namespace dllm {
 int fail(int code, const std::string &msg);
@@ -100,6 +101,87 @@ int search_shape_ok(size_t rows, size_t dim) {
     if (rows >= (size_t(1) << 31))
         return dllm::fail(DLLM_ERR_SHAPE_MISMATCH, "rows must be below 2^31 (the index is an int32)");
     return DLLM_OK;
+}
+
+// ---- the token readout rule in plain C++ (include/dllm_quant.h 8h; csrc/token.hip is the device form) ----
+
+float half_bits_to_float(uint16_t h) {   // exact widening of an IEEE binary16
+    const uint32_t sign = static_cast<uint32_t>(h & 0x8000u) << 16, em = h & 0x7fffu;
+    uint32_t b;
+    if (em >= 0x7c00u) {
+        b = sign | 0x7f800000u | (static_cast<uint32_t>(em & 0x3ffu) << 13);   // inf, NaN
+    } else if (em >= 0x0400u) {
+        b = sign | ((em << 13) + (112u << 23));                                 // normal
+    } else {
+        const float f = static_cast<float>(em) * 0x1p-24f;                      // denormal or zero: exact
+        std::memcpy(&b, &f, 4);
+        b |= sign;
+    }
+    float f;
+    std::memcpy(&f, &b, 4);
+    return f;
+}
+
+// The halving tree of 8f over 256 lane sums.
+float tree256(float *s) {
+    for (int h = 128; h > 0; h >>= 1)
+        for (int j = 0; j < h; ++j) s[j] = s[j] + s[j + h];
+    return s[0];
+}
+
+constexpr size_t kTokenChunk = 16384;
+
+// One row of V widened logits -> token, {m, Z}.
+void token_row_host(const float *x, size_t V, int32_t *token, float *stats) {
+    const float inf = std::numeric_limits<float>::infinity(), qnan = dllm::token::exp_le0(std::nanf(""));
+    // 1. the closed form of the fold
+    ptrdiff_t n = -1;
+    for (size_t i = 0; i < V; ++i)
+        if (x[i] != x[i]) n = static_cast<ptrdiff_t>(i);
+    size_t tok = V - 1;
+    if (static_cast<size_t>(n + 1) < V) {
+        tok = static_cast<size_t>(n + 1);
+        for (size_t i = tok + 1; i < V; ++i)
+            if (!(x[tok] > x[i])) tok = i;
+    }
+    *token = static_cast<int32_t>(tok);
+    if (n >= 0) {
+        stats[0] = stats[1] = qnan;
+        return;
+    }
+    // 3. chunk partials (no NaN from here on)
+    const size_t C = (V + kTokenChunk - 1) / kTokenChunk;
+    std::vector<float> mc(C), Zc(C);
+    float m = -inf;
+    for (size_t c = 0; c < C; ++c) {
+        const size_t lo = c * kTokenChunk, hi = std::min(V, lo + kTokenChunk);
+        float mm = -inf;
+        for (size_t i = lo; i < hi; ++i) mm = x[i] > mm ? x[i] : mm;
+        mm = mm + 0.0f;
+        mc[c] = mm;
+        m = mm > m ? mm : m;
+        if (mm == -inf || mm == inf) {
+            Zc[c] = mm == inf ? qnan : 0.0f;
+            continue;
+        }
+        float lane[256];
+        for (float &l : lane) l = 0.0f;
+        for (size_t i = lo; i < hi; ++i) {   // ascending i: each lane meets its groups in increasing g, components 0..3
+            float &l = lane[((i - lo) / 4) % 256];
+            l = l + dllm::token::exp_le0(x[i] - mm);
+        }
+        Zc[c] = tree256(lane);
+    }
+    // 4. the row
+    stats[0] = m;
+    if (m == -inf || m == inf) {
+        stats[1] = m == inf ? qnan : 0.0f;
+        return;
+    }
+    float lane[256];
+    for (float &l : lane) l = 0.0f;
+    for (size_t c = 0; c < C; ++c) lane[c % 256] = lane[c % 256] + (mc[c] == -inf ? 0.0f : Zc[c] * dllm::token::exp_le0(mc[c] - m));
+    stats[1] = tree256(lane);
 }
 
 #define STAGE_OK(s) \
@@ -304,6 +386,31 @@ int dllm_search_vectors_host(const float *Q, size_t nq, const uint8_t *codes, co
             idx[j * k + i] = i < top ? static_cast<int32_t>(id) : -1;
             scores[j * k + i] = i < top ? sc[id] : -std::numeric_limits<float>::infinity();
         }
+    }
+    return DLLM_OK;
+}
+
+int dllm_token_readout_host(const void *logits, int dtype, size_t M, size_t V, size_t ld, int32_t *tokens,
+                            float *stats, float *probs) {
+    if (V == 0) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "V == 0: no token to read out of an empty vocabulary");
+    if (ld < V) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least V");
+    if (V >= (size_t(1) << 31))
+        return dllm::fail(DLLM_ERR_SHAPE_MISMATCH, "V must be below 2^31 (the token is an int32)");
+    if (dtype != DLLM_F32 && dtype != DLLM_F16)
+        return dllm::fail(DLLM_ERR_UNSUPPORTED, "dtype must be DLLM_F32 or DLLM_F16");
+    if (M == 0) return DLLM_OK;
+    if (!logits || !tokens || !stats) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    const float ninf = -std::numeric_limits<float>::infinity(), qnan = dllm::token::exp_le0(std::nanf(""));
+    std::vector<float> x(V);
+    for (size_t b = 0; b < M; ++b) {
+        for (size_t i = 0; i < V; ++i)
+            x[i] = dtype == DLLM_F16 ? half_bits_to_float(static_cast<const uint16_t *>(logits)[b * ld + i])
+                                     : static_cast<const float *>(logits)[b * ld + i];
+        token_row_host(x.data(), V, tokens + b, stats + 2 * b);
+        if (!probs) continue;
+        const float m = stats[2 * b], Z = stats[2 * b + 1];
+        const bool undefined = Z != Z || m == ninf;
+        for (size_t i = 0; i < V; ++i) probs[b * V + i] = undefined ? qnan : dllm::token::exp_le0(x[i] - m) / Z;
     }
     return DLLM_OK;
 }

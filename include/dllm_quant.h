@@ -561,6 +561,77 @@ int dllm_search_vectors(const float *Q, size_t nq, const uint8_t *codes, const f
                         size_t k, int32_t *idx /* [nq][k] */, float *scores /* [nq][k] */,
                         void *workspace, size_t workspace_bytes, dllm_stream_t stream);
 
+/* ---- 8h token readout: greedy tokens and softmax probabilities over the vocabulary ---------------
+ * DiffusionPrefill::generate (diffusion_prefill/src/lib.rs:117-139) predicts, then samples a token,
+ * until [EOS].  predict_next_token (:141-159, "Convert logits to probabilities") is a placeholder
+ * that returns the uniform vector; sample_token (:162-174) is
+ * probs.iter().enumerate().max_by(|a, b| a.partial_cmp(b).unwrap_or(Equal)).  This section is that
+ * step on device logits [M][V] (row stride ld >= V elements, f32, or f16 widened exactly): per row
+ * the greedy token, stats = {m, Z} and, on request, the probabilities.
+ *
+ * The rule (the contract: a row's bits depend on that row's V elements alone -- not on M, ld, the
+ * alignment, the grid or the device; nothing at or past index V of a row is ever read).
+ * 1. Token.  The reference's fold, on the logits x: cur = 0; for i in 1..V: if !(x[cur] > x[i])
+ *    cur = i (max_by keeps the later element unless the earlier is strictly greater; unwrap_or(Equal)
+ *    makes a NaN equal to everything).  Closed form: with n the index of the last NaN (-1 if none),
+ *    the token is V-1 when n == V-1, else the largest i > n with x[i] == max(x[n+1 .. V)).  -0 equals
+ *    +0 and the later wins; a value before the last NaN never wins; constant logits give V-1 (what
+ *    the reference's uniform placeholder returns).  The form is associative over ordered pieces
+ *    carrying (last NaN, best value, best index or none): a right piece with a NaN replaces the left
+ *    one, otherwise the better best wins and ties go to the right -- so any split over lanes and
+ *    chunks gives the fold's answer.  Deviation: the reference compares probabilities, the build
+ *    compares logits; rounding or underflow of the exponentials cannot then merge two different
+ *    logits into a tie.
+ * 2. EXP: the library's own f32 exponential for arguments <= 0 (csrc/token_exp.hpp states the
+ *    argument reduction and the coefficients): f32 add, multiply, fmaf, an exact scaling by 2^k and
+ *    integer ops only.  EXP(0) == 1 exactly; EXP(NaN) is the quiet NaN 0x7fc00000; EXP(d) == +0 for
+ *    every d < -87 (-inf included), so no denormal is ever produced (exp(-87) = 1.39 * 2^-126).
+ *    Largest error, measured against the exact value over every f32 in [-87, 0]: e = 0.9371 ulp.
+ * 3. Chunk partials.  Chunk c = elements [16384 c, 16384 (c + 1)) of the row.  m_c = the maximum of
+ *    the chunk's non-NaN elements (a zero maximum counts as +0), -inf if there are none.  m_c == -inf
+ *    -> Z_c = +0 (a fully masked vocabulary range does not poison the row).  A NaN in the chunk, or
+ *    m_c == +inf -> Z_c = NaN.  Otherwise Z_c = sum of e_i = EXP(RN(x_i - m_c)) in the summation order
+ *    of 8f, unchanged: groups of four to 256 lanes round-robin (group g = chunk elements 4g .. 4g + 3,
+ *    lane g mod 256); a lane adds its groups in increasing g, components 0, 1, 2, 3, from +0; the
+ *    lanes combine by the halving tree s[j] = s[j] + s[j + h], j < h, h = 128 ... 1; elements at
+ *    index >= V count as +0.
+ * 4. Row.  A NaN anywhere in the row -> stats = {NaN, NaN} (0x7fc00000).  Else m = max_c m_c;
+ *    m == -inf (a row of -inf) -> {-inf, +0};  m == +inf -> {+inf, NaN};  else Z = the sum over c of
+ *    RN(Z_c EXP(RN(m_c - m))) (a term with m_c == -inf is +0), the C = ceil(V / 16384) terms to 256
+ *    lanes round-robin (term c to lane c mod 256, increasing c, from +0) and through the same tree.
+ *    Z >= 1 for every finite row.  Such rows still get their token, and touch no other row.
+ *    EXP(0) == 1 makes RN(1.0f / Z) the probability of the greedy token when the row holds no NaN.
+ * 5. Probabilities (optional).  p_i = RN(EXP(RN(x_i - m)) / Z), the IEEE division, with the row's m
+ *    and Z; every p_i of a row whose Z is NaN or whose m is -inf is the quiet NaN 0x7fc00000.
+ * Error bound, to first order, for a finite row; u = 2^-24, e = EXP's measured error in ulps (one
+ * ulp <= 2 u relative), C chunks, d_i = |x_i - m|.  Every term is >= 0, so as in 8f relative errors
+ * of terms carry to the sum:  a chunk term exp(x_i - m) = exp(x_i - m_c) exp(m_c - m) carries
+ * d_i u (RN(x_i - m_c) and RN(m_c - m) each move their argument by at most u times its size, and
+ * |x_i - m_c| + |m_c - m| = d_i) + 2 (2 e u) (two EXPs) + (64 + 8) u (the lane's adds and the tree) +
+ * u (the product) + (ceil(C / 256) + 8) u (the row's adds and tree).  With D = max_i d_i:
+ *    |Z - sum_i exp(x_i - m)| <= (D + 4 e + 81 + ceil(C / 256)) u * sum_i exp(x_i - m)
+ *    |p_i - softmax_i|        <= (d_i + D + 6 e + 82 + ceil(C / 256)) u * softmax_i + 2^-125
+ * (p_i adds d_i u for RN(x_i - m), 2 e u for its EXP and u for the division; 2^-125 covers EXP's
+ * cut-off -- below it the exact term is under exp(-87) < 2^-125 and the result is +0 -- and a
+ * quotient in the denormal range, which rounds by at most 2^-150).
+ * Checks, in this order, before anything touches the device:
+ * V == 0 or ld < V -> INVALID_PARAMS; V >= 2^31 -> SHAPE_MISMATCH; a dtype other than DLLM_F32 /
+ * DLLM_F16 -> UNSUPPORTED; M == 0 -> DLLM_OK, nothing written; a NULL logits, tokens, stats or
+ * workspace, a workspace not 4-byte aligned or shorter than dllm_token_readout_workspace(M, V) ->
+ * INVALID_PARAMS.  (M ceil(V / 16384) >= 2^31 -> UNSUPPORTED: the grid.) */
+/* Bytes of device workspace dllm_token_readout needs (the chunk pieces): M * ceil(V / 16384) * 20. */
+size_t dllm_token_readout_workspace(size_t M, size_t V);
+/* tokens (device i32 [M]), stats (device f32 [M][2] = {m, Z}) and, when probs != NULL, probs (device
+ * f32 [M][V], contiguous) of logits (device [M] rows of V, stride ld elements, aligned to the
+ * element size).  Any alignment of logits and any ld give the same bits: a group of four is one load
+ * in every layout; with logits aligned to a group (16 bytes for f32, 8 for f16) and ld % 4 == 0 no
+ * group straddles a cache line, which is the fastest layout.
+ * Asynchronous on `stream`; never synchronises or allocates (graph-capturable from the first call);
+ * no atomics. */
+int dllm_token_readout(const void *logits, int dtype, size_t M, size_t V, size_t ld, int32_t *tokens,
+                       float *stats /* [M][2] */, float *probs /* [M][V] or NULL */, void *workspace,
+                       size_t workspace_bytes, dllm_stream_t stream);
+
 /* ---- host-slice variants (synchronous; stage through device memory; not graph-capturable) ----
  * The literal shapes of the reference's Rust signatures, for callers holding host slices. */
 /* quantize_tensor(&[f32], u8) -> (Vec<u8>, f32, f32): codes one per byte (quantization.rs:38-68). */
@@ -592,6 +663,10 @@ int dllm_search_table_host(const uint8_t *codes, size_t rows, size_t dim, const 
                            float *table /* [rows][2] */);
 int dllm_search_vectors_host(const float *Q, size_t nq, const uint8_t *codes, const float *table, size_t rows,
                              size_t dim, size_t k, int32_t *idx /* [nq][k] */, float *scores /* [nq][k] */);
+/* dllm_token_readout on host slices: the rule of section 8h in plain C++ (no device, no staging, no
+ * workspace), the same bits as the kernels; the same checks and codes. */
+int dllm_token_readout_host(const void *logits, int dtype, size_t M, size_t V, size_t ld, int32_t *tokens,
+                            float *stats /* [M][2] */, float *probs /* [M][V] or NULL */);
 
 #ifdef __cplusplus
 }
