@@ -39,10 +39,12 @@ int alpha_tables(const float *betas, size_t T, int cumprod, std::vector<float> &
 // x_prev = (c1 x_t + c2 eps) + std * n over rows of D; n = noise[i] (given), the generated stream
 // element offset + i (noise == nullptr), or 0 (add == 0).  Four consecutive elements per thread:
 // one Philox block when offset % 4 == 0.
-__global__ void __launch_bounds__(256) p_sample_kernel(const float *__restrict__ x, const float *__restrict__ eps,
+// out may be x or eps (dllm_p_sample: x_prev may alias x_t or eps): every element is read before it
+// is written, by the one thread that owns it, so those three carry no __restrict__.
+__global__ void __launch_bounds__(256) p_sample_kernel(const float *x, const float *eps,
                                                        const float *__restrict__ noise, const float *__restrict__ coef,
                                                        size_t n, size_t D, int add, uint64_t seed, uint64_t offset,
-                                                       float *__restrict__ out) {
+                                                       float *out) {
     const size_t nq = (n + 3) / 4;
     for (size_t q = blockIdx.x * static_cast<size_t>(256) + threadIdx.x; q < nq;
          q += static_cast<size_t>(gridDim.x) * 256) {
@@ -79,9 +81,10 @@ __global__ void __launch_bounds__(256) p_sample_kernel(const float *__restrict__
 }
 
 // noisy = x0 sqrt(abar) + n sqrt(1 - abar); n given or generated (then optionally written out).
-__global__ void __launch_bounds__(256) add_noise_kernel(const float *__restrict__ x0, const float *__restrict__ noise,
+// out may be x0 (dllm_add_noise: noisy may alias x0), so neither carries __restrict__.
+__global__ void __launch_bounds__(256) add_noise_kernel(const float *x0, const float *__restrict__ noise,
                                                         const float *__restrict__ coef, size_t n, size_t D,
-                                                        uint64_t seed, uint64_t offset, float *__restrict__ out,
+                                                        uint64_t seed, uint64_t offset, float *out,
                                                         float *__restrict__ noise_out) {
     const size_t nq = (n + 3) / 4;
     for (size_t q = blockIdx.x * static_cast<size_t>(256) + threadIdx.x; q < nq;
@@ -107,9 +110,9 @@ __global__ void __launch_bounds__(256) randn_kernel(uint64_t seed, uint64_t offs
     const size_t nq = (n + 3) / 4;
     for (size_t q = blockIdx.x * static_cast<size_t>(256) + threadIdx.x; q < nq;
          q += static_cast<size_t>(gridDim.x) * 256) {
-        float z[4];
-        rng::normal4(seed, offset / 4 + q, z);
         const size_t i0 = q * 4;
+        float z[4];
+        rng::normal4(seed, (offset + i0) / 4, z);   // the stream index wraps modulo 2^64, as in every consumer
         if (i0 + 4 <= n) {
             *reinterpret_cast<float4 *>(out + i0) = make_float4(z[0], z[1], z[2], z[3]);
         } else {
@@ -208,7 +211,8 @@ __global__ void __launch_bounds__(kMseLanes) noise_mse_chunk_kernel(const T *__r
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float z[4];
-                rng::normal4(seed, (offset + base + i) / 4 + static_cast<size_t>(k) * kMseLanes, z);
+                // the index wraps modulo 2^64 before the division, as in the ragged branch below
+                rng::normal4(seed, (offset + base + i + static_cast<size_t>(k) * (4 * kMseLanes)) / 4, z);
                 s = mse_add4(s, make_float4(z[0], z[1], z[2], z[3]), p[k]);
             }
         }
@@ -386,6 +390,7 @@ int dllm_randn(uint64_t seed, uint64_t offset, float *out, size_t n, dllm_stream
     if (n == 0) return DLLM_OK;
     if (!out) return fail(DLLM_ERR_INVALID_PARAMS, "out is NULL");
     if (offset % 4) return fail(DLLM_ERR_INVALID_PARAMS, "offset must be a multiple of 4");
+    if (reinterpret_cast<uintptr_t>(out) % 16) return fail(DLLM_ERR_INVALID_PARAMS, "out must be 16-byte aligned");
     randn_kernel<<<elem_grid(n), 256, 0, as_stream(stream)>>>(seed, offset, n, out);
     DLLM_LAUNCH_CHECK();
     return DLLM_OK;

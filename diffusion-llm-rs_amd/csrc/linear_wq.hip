@@ -1688,7 +1688,9 @@ int dllm_linear_forward_psample_ex(dllm_linear_t h, const void *X, size_t M, int
         }
         return DLLM_OK;
     }
-    const PSampleEpi ep{x_t, coef, static_cast<int>(rows_per_sample), add_noise ? 1 : 0, seed, offset, x_prev, noise,
+    // rows_per_sample >= M is "one sample": every m / rps is 0, and min(., M) fits the epilogue's int
+    const int rps = static_cast<int>(std::min(rows_per_sample, M));
+    const PSampleEpi ep{x_t, coef, rps, add_noise ? 1 : 0, seed, offset, x_prev, noise,
                         static_cast<__half *>(x_prev_f16)};
     switch (h->bits) {
     case 2: return psample_fused<2>(h, Xh, (int)M, ep, st);

@@ -425,7 +425,10 @@ int dllm_kv_attention_hd(const void *Q, size_t Sq, const void *K, const float *k
  * Noise: the reference draws rand::thread_rng normals (unseeded); the build uses a seeded
  * counter-based stream: element e of (seed) = Philox4x32-10(key seed, counter e/4) + a Box-Muller
  * of correctly rounded + - * / sqrt only (bit-reproducible on any IEEE host; see
- * csrc/diffusion_rng.hpp).  Stream offsets must be multiples of 4. */
+ * csrc/diffusion_rng.hpp).  Stream offsets must be multiples of 4.  The stream index "offset + i"
+ * of every entry point that draws from the stream (dllm_randn, dllm_p_sample, dllm_add_noise,
+ * dllm_linear_forward_psample[_ex], dllm_noise_mse) is taken modulo 2^64: past element 2^64 - 1
+ * the stream continues with element 0. */
 enum dllm_beta_kind { DLLM_BETA_LINEAR = 0, DLLM_BETA_QUADRATIC = 1, DLLM_BETA_COSINE = 2 };
 enum dllm_cumprod { DLLM_ABAR_EXCLUSIVE = 0, DLLM_ABAR_INCLUSIVE = 1 };
 enum dllm_alpha_mode { DLLM_ALPHA_PER_SAMPLE = 0, DLLM_ALPHA_LITERAL = 1 };
@@ -440,16 +443,20 @@ int dllm_p_sample_coeffs(const float *betas, size_t T, int cumprod, int alpha_mo
                          float *coef, int *add_noise);
 /* add_noise scalars (lib.rs:1121-1133): coef[B][2] = {sqrt(abar_t), sqrt(1 - abar_t)}. Host arrays. */
 int dllm_add_noise_coeffs(const float *betas, size_t T, int cumprod, const size_t *t, size_t B, float *coef);
-/* out[i] = element offset + i of the seeded N(0,1) stream (device). */
+/* out[i] = element offset + i of the seeded N(0,1) stream (device).  out 16-byte aligned and
+ * offset % 4 == 0, else DLLM_ERR_INVALID_PARAMS and nothing is launched. */
 int dllm_randn(uint64_t seed, uint64_t offset, float *out, size_t n, dllm_stream_t stream);
 /* p_sample elementwise step (lib.rs:1197-1212) on B rows of D (device f32; coef device [B][3]):
  * x_prev = (c1 x_t + c2 eps) + std * n, n = noise[i] if noise != NULL, else stream element
- * offset + i of `seed`; n = 0 when add_noise == 0.  x_t, eps, x_prev 16-byte aligned. */
+ * offset + i of `seed`; n = 0 when add_noise == 0 (noise is then not read).  x_t, eps, x_prev
+ * 16-byte aligned (noise at any f32 alignment); offset % 4 == 0 when noise == NULL; else
+ * DLLM_ERR_INVALID_PARAMS and nothing is launched.  x_prev may alias x_t or eps (in place). */
 int dllm_p_sample(const float *x_t, const float *eps, const float *noise, const float *coef, size_t B, size_t D,
                   int add_noise, uint64_t seed, uint64_t offset, float *x_prev, dllm_stream_t stream);
 /* add_noise forward step (lib.rs:1130-1135): noisy = x0 sqrt(abar) + n sqrt(1 - abar) on B rows
  * of D; n = noise (device) or the stream (noise == NULL; then written to noise_out if non-NULL,
- * the reference's returned noise). */
+ * the reference's returned noise; offset % 4 == 0 then, else DLLM_ERR_INVALID_PARAMS).  Pointers at
+ * any f32 alignment.  noisy may alias x0 (in place). */
 int dllm_add_noise(const float *x0, const float *noise, const float *coef, size_t B, size_t D, uint64_t seed,
                    uint64_t offset, float *noisy, float *noise_out, dllm_stream_t stream);
 /* Denoiser output layer fused with p_sample: eps = X . W^ + b (f32, as dllm_linear_forward with
@@ -458,7 +465,8 @@ int dllm_add_noise(const float *x0, const float *noise, const float *coef, size_
  * sample m / rows_per_sample) and n = noise[m][n] when noise != NULL (f32 [M][N], e.g. drawn by
  * dllm_randn on a side stream while the earlier layers run), else stream element offset + m N + n
  * generated in the epilogue.  Bit-identical to dllm_linear_forward(..., DLLM_F32) followed by
- * dllm_p_sample with the same noise.  N % 4 == 0. */
+ * dllm_p_sample with the same noise.  N % 4 == 0.  rows_per_sample >= M means one sample (every
+ * row uses coef[0]); 0 -> DLLM_ERR_INVALID_PARAMS. */
 int dllm_linear_forward_psample(dllm_linear_t h, const void *X, size_t M, int x_dtype, const float *x_t,
                                 const float *coef, size_t rows_per_sample, int add_noise, uint64_t seed,
                                 uint64_t offset, const float *noise, float *x_prev, dllm_stream_t stream);
