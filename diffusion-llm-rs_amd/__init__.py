@@ -21,11 +21,15 @@ this package is the host-side mirror of the reference's Rust operator surface:
 * ``decode``       -- the token readout (``DiffusionPrefill``'s predict / ``sample_token`` step): greedy
   tokens, {max, softmax denominator} and probabilities of logits [M, vocab] in a pinned,
   bit-reproducible rule: token_readout, TokenHead.
+* ``dedup``        -- ``IODedupEngine::store_vectors`` on the device, between ``compress_vectors`` and
+  the search: the reference's u64 hash of each row's codes, the first-occurrence filter over a
+  caller-owned seen-set and the gather of the kept rows: hash_rows, dedup_rows, DedupBuffer,
+  store_vectors.
 """
 from . import _lib
 from ._lib import (CalibrationRequired, HipError, InvalidParams, QuantizationError, SerializationError,
                    ShapeMismatch, UnsupportedOperation)
-from . import quantization, quant, kvquant, linear, parallel, diffusion, serde, search, decode
+from . import quantization, quant, kvquant, linear, parallel, diffusion, serde, search, decode, dedup
 from .quantization import (AdaptiveQuantizer, QuantizedKVCacheEntry, QuantizedTensor, compression_ratio, dequantize_tensor, kv_attention,
                            pack, quantize_tensor, quantize_tensor_pair, unpack)
 from .quant import CalibrationData, DefaultQuantizer, QuantizationParams, QuantizationType, quant_utils
@@ -36,6 +40,7 @@ from .diffusion import (AlphaMode, BetaSchedule, Cumprod, DenoiseLoop, Diffusion
                         p_sample, randn)
 from .search import VectorIndex, search_table, search_vectors
 from .decode import TokenHead, token_readout
+from .dedup import DedupBuffer, dedup_rows, gather_rows, hash_rows, store_vectors
 
 __all__ = [
     "quantize_tensor", "quantize_tensor_pair", "dequantize_tensor", "pack", "unpack", "compression_ratio", "QuantizedTensor",
@@ -45,7 +50,7 @@ __all__ = [
     "ShapeMismatch", "CalibrationRequired", "HipError", "BetaSchedule", "Cumprod", "AlphaMode", "DiffusionConfig",
     "KVCacheEntry", "KVCacheStore", "DenoiseLoop", "add_noise", "p_sample", "randn", "AdaptiveQuantizer",
     "noise_mse", "p_losses", "p_losses_coeffs", "search_vectors", "search_table", "VectorIndex",
-    "token_readout", "TokenHead",
+    "token_readout", "TokenHead", "hash_rows", "dedup_rows", "gather_rows", "DedupBuffer", "store_vectors",
 ]
 
 

@@ -164,6 +164,16 @@ SIGNATURES = {
     "dllm_token_readout_workspace": (S, [S, S]),
     "dllm_token_readout": (INT, [P, INT, S, S, S, P, P, P, P, S, P]),
     "dllm_token_readout_host": (INT, [P, INT, S, S, S, P, P, P]),
+    "dllm_hash_rows": (INT, [P, S, S, S, P, P]),
+    "dllm_dedup_table_bytes": (S, [S]),
+    "dllm_dedup_table_init": (INT, [P, S, P]),
+    "dllm_dedup_workspace": (S, [S]),
+    "dllm_dedup_rows": (INT, [P, S, U64, P, S, P, P, P, P, P, S, P]),
+    "dllm_gather_rows": (INT, [P, S, S, P, P, P, S, P]),
+    "dllm_hash_rows_host": (INT, [P, S, S, S, P]),
+    "dllm_dedup_table_init_host": (INT, [P, S]),
+    "dllm_dedup_rows_host": (INT, [P, S, U64, P, S, P, P, P, P]),
+    "dllm_gather_rows_host": (INT, [P, S, S, P, P, P, S]),
     "dllm_quantize_tensor_host": (INT, [P, S, U8, P, P, P]),
     "dllm_dequantize_tensor_host": (INT, [P, S, FL, FL, P]),
     "dllm_default_quantize_host": (INT, [P, S, INT, FL, I32, P]),

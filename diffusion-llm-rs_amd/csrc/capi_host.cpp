@@ -9,8 +9,10 @@
 #include <functional>
 #include <limits>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
+#include "dedup_rule.hpp"
 #include "dllm_quant.h"
 #include "token_exp.hpp"
 
@@ -412,6 +414,97 @@ int dllm_token_readout_host(const void *logits, int dtype, size_t M, size_t V, s
         const bool undefined = Z != Z || m == ninf;
         for (size_t i = 0; i < V; ++i) probs[b * V + i] = undefined ? qnan : dllm::token::exp_le0(x[i] - m) / Z;
     }
+    return DLLM_OK;
+}
+
+// ---- the dedup rules in plain C++ (include/dllm_quant.h 8i; csrc/dedup.hip is the device form) ----
+
+int dllm_hash_rows_host(const uint8_t *codes, size_t rows, size_t dim, size_t ld, uint64_t *hashes) {
+    if (dim == 0 || dim > dllm::dedup::kMaxDim) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "dim must be between 1 and 65535");
+    if (ld < dim) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least dim");
+    if (rows >= (size_t(1) << 31)) return dllm::fail(DLLM_ERR_SHAPE_MISMATCH, "rows must be below 2^31");
+    if (rows == 0) return DLLM_OK;
+    if (!codes || !hashes) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    for (size_t r = 0; r < rows; ++r) {   // compute_hash, io-dedup/src/lib.rs:161-166
+        uint64_t acc = 0;
+        for (size_t i = 0; i < dim; ++i) acc = acc * 31u + codes[r * ld + i];
+        hashes[r] = acc;
+    }
+    return DLLM_OK;
+}
+
+int dllm_dedup_table_init_host(void *table, size_t slots) {
+    using namespace dllm::dedup;
+    if (!is_pow2(slots) || slots > (size_t(1) << 56)) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "slots must be a power of two");
+    if (!table) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    uint64_t *t = static_cast<uint64_t *>(table);
+    std::fill(t, t + table_words(slots), ~uint64_t(0));
+    t[kFlagWord] = t[kCountWord] = t[3] = 0;
+    return DLLM_OK;
+}
+
+int dllm_dedup_rows_host(const uint64_t *hashes, size_t rows, uint64_t base, void *table, size_t slots, uint8_t *keep,
+                         uint64_t *first, int32_t *kept_rows, uint32_t *n_kept) {
+    using namespace dllm::dedup;
+    if (rows >= (size_t(1) << 31))
+        return dllm::fail(DLLM_ERR_SHAPE_MISMATCH, "rows must be below 2^31 (a kept row's index is an int32)");
+    if (base >= (uint64_t(1) << 62)) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "base must be below 2^62");
+    if (table) {
+        if (!is_pow2(slots) || slots > (size_t(1) << 56))
+            return dllm::fail(DLLM_ERR_INVALID_PARAMS, "slots must be a power of two");
+        if (reinterpret_cast<uintptr_t>(table) % 8) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "table must be 8-byte aligned");
+        if (base + rows > slots / 2)
+            return dllm::fail(DLLM_ERR_INVALID_PARAMS, "base + rows exceeds slots / 2: the seen-set is kept at most half full");
+    }
+    if (rows == 0) return DLLM_OK;
+    if (!hashes || !keep || !first || !kept_rows || !n_kept) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    std::unordered_map<uint64_t, uint64_t> seen;   // the one-shot form's set: hash -> first sequence number
+    uint64_t *t = static_cast<uint64_t *>(table);
+    uint32_t n = 0;
+    for (size_t r = 0; r < rows; ++r) {             // deduplicate, io-dedup/src/lib.rs:145-159
+        const uint64_t h = hashes[r], seq = base + r;
+        uint64_t *val = nullptr;                    // where this hash's first sequence number lives
+        bool fresh = false;
+        if (!t) {
+            auto ins = seen.emplace(h, seq);
+            val = &ins.first->second, fresh = ins.second;
+        } else if (h == kEmptyKey) {
+            val = t + kSideWord, fresh = *val == kNoSeq;
+        } else {
+            uint64_t *keys = t + kHeaderWords, *vals = keys + slots;
+            size_t s = first_slot(h, slots - 1);
+            for (size_t probe = 0; probe < slots && !val; ++probe) {
+                if (keys[s] == kEmptyKey) keys[s] = h, fresh = true;
+                if (keys[s] == h) val = vals + s;
+                s = (s + 1) & (slots - 1);
+            }
+        }
+        if (!val) {                                 // no slot left: only a dishonest base gets here
+            t[kFlagWord] = 1;
+            keep[r] = 0, first[r] = kNoSeq;
+            continue;
+        }
+        if (fresh) {
+            *val = seq;
+            if (t) ++t[kCountWord];
+        }
+        keep[r] = fresh ? 1 : 0;
+        first[r] = *val;
+        if (fresh) kept_rows[n++] = static_cast<int32_t>(r);
+    }
+    *n_kept = n;
+    for (size_t i = n; i < rows; ++i) kept_rows[i] = -1;
+    return DLLM_OK;
+}
+
+int dllm_gather_rows_host(const uint8_t *codes, size_t dim, size_t ld, const int32_t *kept_rows, const uint32_t *n_kept,
+                          uint8_t *out, size_t out_ld) {
+    if (dim == 0 || dim > dllm::dedup::kMaxDim) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "dim must be between 1 and 65535");
+    if (ld < dim) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least dim");
+    if (out_ld < dim) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "out_ld must be at least dim");
+    if (!codes || !kept_rows || !n_kept || !out) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    for (size_t i = 0; i < *n_kept; ++i)            // merge_requests' concat, io-dedup/src/lib.rs:181-212
+        if (kept_rows[i] >= 0) std::memcpy(out + i * out_ld, codes + static_cast<size_t>(kept_rows[i]) * ld, dim);
     return DLLM_OK;
 }
 

@@ -640,6 +640,85 @@ int dllm_token_readout(const void *logits, int dtype, size_t M, size_t V, size_t
                        float *stats /* [M][2] */, float *probs /* [M][V] or NULL */, void *workspace,
                        size_t workspace_bytes, dllm_stream_t stream);
 
+/* ---- 8i dedup: hash, filter and merge the CompressedVector store on the device ---------------------
+ * IODedupEngine::store_vectors (io-dedup/src/lib.rs:119-135) is the reference's write path for
+ * CompressedVector records: compute_hash (:161-166) of each record's code bytes, deduplicate
+ * (:145-159) drops every record whose hash was seen before, in this batch or an earlier one,
+ * merge_requests (:181-212) concatenates the survivors in order.  This section is those three steps on
+ * what dllm_compress_vectors emits (codes u8 [rows][dim], one code per byte), between the ingest and
+ * dllm_search_*.  All of it is integer arithmetic: the device, the _host mirrors and any restatement
+ * agree to the bit; no output depends on the grid, the arrival order of threads or the device.
+ *
+ * Rule 1, the hash.  h(row) = fold(0u64, |acc, b| acc * 31 + b) over the row's dim code bytes in
+ * wrapping u64 arithmetic, i.e. h = sum_i b_i 31^(dim - 1 - i) mod 2^64: any split into pieces is
+ * exact and the sum over pieces is order-free.  The all-zero row hashes to 0.
+ *
+ * Rule 2, the filter.  Row r of a call has the sequence number base + r, `base` being the number of
+ * rows offered to the same seen-set before this call.  A row is KEPT iff no row with a smaller
+ * sequence number -- earlier in this call, or in any earlier call on the same seen-set -- has the
+ * same hash.  first[r] = the smallest sequence number ever offered with row r's hash (its own, if
+ * kept).
+ *   EQUAL HASH MEANS DUPLICATE, EXACTLY AS IN THE REFERENCE: its seen_hashes map stores the bytes
+ *   beside the hash, but nothing ever compares them.  Two rows with different bytes and the same hash
+ *   (e.g. {1, 31} and {2, 0}: both 62) are one record to this filter: THE LATER ONE IS DROPPED.  A
+ *   caller who cares compares the bytes of row r and of row first[r] itself.
+ *   kept_rows = the indices of the kept rows, ascending (the order of the reference's `unique`
+ *   vector), then -1 to the end of its `rows` entries; n_kept = their number.
+ *   The seen-set is caller-owned memory of dllm_dedup_table_bytes(slots) bytes, slots a power of two,
+ *   initialised by dllm_dedup_table_init: an open-addressing table (csrc/dedup_rule.hpp states the
+ *   words) that is never allowed to be more than half full.  The caller keeps `base` and the entry
+ *   rejects base + rows > slots / 2 before launching anything: the host needs no count from the
+ *   device.  `base` counts EVERY row offered since dllm_dedup_table_init, duplicates included, and
+ *   must never be lowered short of a new init: sequence numbers would repeat, a later row could
+ *   undercut the stored first occurrence of its hash and be KEPT although it is a duplicate, and
+ *   `first` of every later row with that hash would change.  Duplicates take no slot, so base
+ *   overstates the distinct hashes held; that only wastes headroom.  Word 1 of the table holds the
+ *   true distinct count; it is informational only.  A caller who passes a base smaller than the truth
+ *   thus keeps duplicates, and can also fill the table: every probe is bounded by `slots`, a row that
+ *   finds no slot sets word 0 of the table (the flag) and comes back keep = 0, first = 2^64 - 1;
+ *   nothing faults or hangs.  Which slot a hash lands in may depend on arrival order; no output does.
+ *   The key value 2^64 - 1 marks an empty slot; a row that hashes to it is tracked in a word of its
+ *   own and filtered like any other.
+ *
+ * Rule 3, the merge.  Row kept_rows[i] of the codes becomes row i of the output, i < n_kept; rows of
+ * the output from n_kept on are not written.  n_kept is read on the device, so hash, filter and merge
+ * chain on one stream without a synchronisation. */
+/* hashes (device u64 [rows]) of codes (device u8, rows of dim bytes, row stride ld bytes).  Every
+ * alignment of codes and every ld give the same bits: a row is read as aligned 16-byte pieces and
+ * the bytes of a piece that lie outside the row are masked off, so bytes of neighbouring rows and of
+ * the ld - dim padding are read (and ignored); nothing outside the buffer [codes, codes + (rows - 1) ld
+ * + dim) is read (the two pieces that would leave it are read byte by byte).  Checked in this
+ * order before anything touches the device: dim == 0 or > 65535, ld < dim -> INVALID_PARAMS; rows >=
+ * 2^31 -> SHAPE_MISMATCH; rows == 0 -> DLLM_OK; a NULL codes or hashes, hashes not 8-byte aligned ->
+ * INVALID_PARAMS.  Asynchronous on `stream`; never synchronises or allocates; no atomics. */
+int dllm_hash_rows(const uint8_t *codes, size_t rows, size_t dim, size_t ld, uint64_t *hashes, dllm_stream_t stream);
+/* Bytes of a seen-set of `slots` slots: (4 + 2 slots) * 8; 0 when slots is no power of two. */
+size_t dllm_dedup_table_bytes(size_t slots);
+/* Empties the seen-set (device memory, 8-byte aligned).  slots no power of two, NULL -> INVALID_PARAMS. */
+int dllm_dedup_table_init(void *table, size_t slots, dllm_stream_t stream);
+/* Bytes of device workspace dllm_dedup_rows needs: a u32 per 1024 rows (rounded up to 16 bytes) and
+ * the table of the one-shot form (the smallest power of two >= 2 rows slots); 0 when rows >= 2^31. */
+size_t dllm_dedup_workspace(size_t rows);
+/* Rule 2 on hashes (device u64 [rows]): keep (u8 [rows], 1 / 0), first (u64 [rows]), kept_rows (i32
+ * [rows]), n_kept (one u32), all device memory.  table == NULL is the one-shot form: a filter within
+ * this batch alone, on an empty seen-set in the workspace (`slots` ignored; sequence numbers still
+ * start at base).  Checked in this order before anything touches the device: rows >= 2^31 ->
+ * SHAPE_MISMATCH; base >= 2^62 -> INVALID_PARAMS; with a table: slots no power of two, table not
+ * 8-byte aligned, base + rows > slots / 2 -> INVALID_PARAMS; rows == 0 -> DLLM_OK, nothing written
+ * (n_kept included); a NULL hashes, keep, first, kept_rows or n_kept -> INVALID_PARAMS; workspace NULL,
+ * shorter than dllm_dedup_workspace(rows) or not 16-byte aligned -> INVALID_PARAMS; hashes / first not
+ * 8-byte, kept_rows / n_kept not 4-byte aligned -> INVALID_PARAMS.
+ * Asynchronous on `stream`; never synchronises or allocates (graph-capturable from the first call).
+ * 64-bit compare-and-swap and atomic min on the table; no thread waits for another's store. */
+int dllm_dedup_rows(const uint64_t *hashes, size_t rows, uint64_t base, void *table, size_t slots,
+                    uint8_t *keep /* [rows] */, uint64_t *first /* [rows] */, int32_t *kept_rows /* [rows] */,
+                    uint32_t *n_kept, void *workspace, size_t workspace_bytes, dllm_stream_t stream);
+/* Rule 3: out (device u8, row stride out_ld >= dim) row i = codes row kept_rows[i] for i < *n_kept
+ * (device).  dim, both strides and both addresses multiples of 16 is the fast path.  dim == 0 or >
+ * 65535, ld < dim, out_ld < dim, a NULL pointer -> INVALID_PARAMS.  Asynchronous on `stream`. */
+int dllm_gather_rows(const uint8_t *codes, size_t dim, size_t ld, const int32_t *kept_rows, const uint32_t *n_kept,
+                     uint8_t *out, size_t out_ld, dllm_stream_t stream);
+
 /* ---- host-slice variants (synchronous; stage through device memory; not graph-capturable) ----
  * The literal shapes of the reference's Rust signatures, for callers holding host slices. */
 /* quantize_tensor(&[f32], u8) -> (Vec<u8>, f32, f32): codes one per byte (quantization.rs:38-68). */
@@ -675,6 +754,17 @@ int dllm_search_vectors_host(const float *Q, size_t nq, const uint8_t *codes, co
  * workspace), the same bits as the kernels; the same checks and codes. */
 int dllm_token_readout_host(const void *logits, int dtype, size_t M, size_t V, size_t ld, int32_t *tokens,
                             float *stats /* [M][2] */, float *probs /* [M][V] or NULL */);
+/* Section 8i on host slices: serial restatements of the reference's loops in plain C++ (no device,
+ * no staging, no workspace), the same bits as the kernels; the same checks and codes, minus the
+ * workspace's.  The seen-set is host memory of the same size and layout (dllm_dedup_table_bytes,
+ * emptied by dllm_dedup_table_init_host); a table copied between host and device stays valid.
+ * table == NULL is the one-shot form. */
+int dllm_hash_rows_host(const uint8_t *codes, size_t rows, size_t dim, size_t ld, uint64_t *hashes);
+int dllm_dedup_table_init_host(void *table, size_t slots);
+int dllm_dedup_rows_host(const uint64_t *hashes, size_t rows, uint64_t base, void *table, size_t slots, uint8_t *keep,
+                         uint64_t *first, int32_t *kept_rows, uint32_t *n_kept);
+int dllm_gather_rows_host(const uint8_t *codes, size_t dim, size_t ld, const int32_t *kept_rows, const uint32_t *n_kept,
+                          uint8_t *out, size_t out_ld);
 
 #ifdef __cplusplus
 }

@@ -379,4 +379,44 @@ inline std::vector<std::pair<std::string, float>> search(const std::vector<Compr
 }
 }  // namespace diffusion_prefill
 
+namespace io_dedup {
+// IODedupEngine's dedup_buffer (io-dedup/src/lib.rs:102-106, 145-166) by dllm_quant.h 8i's rules (host
+// form): remembers the hash of every record offered until it is destroyed.  `capacity` is the number
+// of records that may be offered in all; offering more throws INVALID_PARAMS.
+class DedupBuffer {
+  public:
+    explicit DedupBuffer(size_t capacity) {
+        while (slots_ < 2 * capacity) slots_ *= 2;
+        table_.resize(dllm_dedup_table_bytes(slots_) / sizeof(uint64_t));
+        detail::check(dllm_dedup_table_init_host(table_.data(), slots_));
+    }
+    static uint64_t compute_hash(const std::vector<uint8_t> &data) {   // :161-166; an empty record hashes to 0
+        uint64_t h = 0;
+        if (!data.empty()) detail::check(dllm_hash_rows_host(data.data(), 1, data.size(), data.size(), &h));
+        return h;
+    }
+    // deduplicate (:145-159): the records whose hash was not seen before, in order.  Equal hash means
+    // duplicate whatever the bytes, as in the reference.
+    std::vector<diffusion_prefill::CompressedVector> deduplicate(const std::vector<diffusion_prefill::CompressedVector> &vectors) {
+        const size_t rows = vectors.size();
+        std::vector<uint64_t> hashes(rows), first(rows);
+        std::vector<uint8_t> keep(rows);
+        std::vector<int32_t> kept(rows);
+        uint32_t n = 0;
+        for (size_t r = 0; r < rows; ++r) hashes[r] = compute_hash(vectors[r].data);
+        detail::check(dllm_dedup_rows_host(hashes.data(), rows, base_, table_.data(), slots_, keep.data(), first.data(),
+                                           kept.data(), &n));
+        base_ += rows;
+        std::vector<diffusion_prefill::CompressedVector> unique;
+        for (uint32_t i = 0; i < n; ++i) unique.push_back(vectors[kept[i]]);
+        return unique;
+    }
+
+  private:
+    size_t slots_ = 2;
+    uint64_t base_ = 0;
+    std::vector<uint64_t> table_;
+};
+}  // namespace io_dedup
+
 }  // namespace dllm
