@@ -20,7 +20,8 @@ this package is the host-side mirror of the reference's Rust operator surface:
   (``FusionANN::search`` over ``KVCache``'s records): search_vectors, VectorIndex.
 * ``decode``       -- the token readout (``DiffusionPrefill``'s predict / ``sample_token`` step): greedy
   tokens, {max, softmax denominator} and probabilities of logits [M, vocab] in a pinned,
-  bit-reproducible rule: token_readout, TokenHead.
+  bit-reproducible rule: token_readout, TokenHead; and the sampling step beside it (temperature,
+  top-k, seeded draws by the same kind of rule): sample_tokens, TokenHead.sample.
 * ``dedup``        -- ``IODedupEngine::store_vectors`` on the device, between ``compress_vectors`` and
   the search: the reference's u64 hash of each row's codes, the first-occurrence filter over a
   caller-owned seen-set and the gather of the kept rows: hash_rows, dedup_rows, DedupBuffer,
@@ -39,7 +40,7 @@ from .diffusion import (AlphaMode, BetaSchedule, Cumprod, DenoiseLoop, Diffusion
                         add_noise, noise_mse, p_losses, p_losses_coeffs,
                         p_sample, randn)
 from .search import VectorIndex, search_table, search_vectors
-from .decode import TokenHead, token_readout
+from .decode import TokenHead, sample_tokens, token_readout
 from .dedup import DedupBuffer, dedup_rows, gather_rows, hash_rows, store_vectors
 
 __all__ = [
@@ -50,7 +51,7 @@ __all__ = [
     "ShapeMismatch", "CalibrationRequired", "HipError", "BetaSchedule", "Cumprod", "AlphaMode", "DiffusionConfig",
     "KVCacheEntry", "KVCacheStore", "DenoiseLoop", "add_noise", "p_sample", "randn", "AdaptiveQuantizer",
     "noise_mse", "p_losses", "p_losses_coeffs", "search_vectors", "search_table", "VectorIndex",
-    "token_readout", "TokenHead", "hash_rows", "dedup_rows", "gather_rows", "DedupBuffer", "store_vectors",
+    "token_readout", "sample_tokens", "TokenHead", "hash_rows", "dedup_rows", "gather_rows", "DedupBuffer", "store_vectors",
 ]
 
 

@@ -15,6 +15,7 @@
 #include "dedup_rule.hpp"
 #include "dllm_quant.h"
 #include "token_exp.hpp"
+#include "token_sample_rule.hpp"
 
 namespace dllm {
 int fail(int code, const std::string &msg);
@@ -184,6 +185,93 @@ void token_row_host(const float *x, size_t V, int32_t *token, float *stats) {
     for (float &l : lane) l = 0.0f;
     for (size_t c = 0; c < C; ++c) lane[c % 256] = lane[c % 256] + (mc[c] == -inf ? 0.0f : Zc[c] * dllm::token::exp_le0(mc[c] - m));
     stats[1] = tree256(lane);
+}
+
+// ---- the token sampling rule in plain C++ (include/dllm_quant.h 8j; csrc/token.hip is the device form) ----
+
+// Rule 5: the first j with t < F_j, F the sequential fold of a[0 .. n) from +0, t = RN(v F_{n-1}); -1 if none.
+ptrdiff_t pick_host(const float *a, size_t n, float v) {
+    float S = 0.0f;
+    for (size_t j = 0; j < n; ++j) S = S + a[j];
+    const float t = v * S;
+    float F = 0.0f;
+    for (size_t j = 0; j < n; ++j) {
+        F = F + a[j];
+        if (t < F) return static_cast<ptrdiff_t>(j);
+    }
+    return -1;
+}
+
+// One row of V widened logits -> token, {m, Z, p_token}.  y is scratch of V floats.
+void token_sample_row_host(const float *x, size_t V, float r, size_t top_k, const float *u, std::vector<float> &y,
+                           int32_t *token, float *stats) {
+    const float inf = std::numeric_limits<float>::infinity(), qnan = dllm::token::exp_le0(std::nanf(""));
+    *token = -1;
+    stats[0] = stats[1] = stats[2] = qnan;
+    // 1. temperature
+    bool nan = false;
+    for (size_t i = 0; i < V; ++i) {
+        y[i] = x[i] * r;
+        nan |= y[i] != y[i];
+    }
+    if (nan) return;
+    // 2. top-k: tau = the k-th largest value; everything below it becomes -inf
+    if (top_k > 0 && top_k < V) {
+        std::vector<float> v(y.begin(), y.end());
+        std::nth_element(v.begin(), v.begin() + static_cast<ptrdiff_t>(top_k - 1), v.end(), std::greater<float>());
+        const float tau = v[top_k - 1];
+        for (size_t i = 0; i < V; ++i)
+            if (!(y[i] >= tau)) y[i] = -inf;
+    }
+    // 3. chunk partials and the row, as 8h.3 and 8h.4 (the lane sums are kept: level 2 picks among them)
+    const size_t C = (V + kTokenChunk - 1) / kTokenChunk;
+    std::vector<float> mc(C), w(C), lanes(C * 256, 0.0f);
+    float m = -inf;
+    for (size_t c = 0; c < C; ++c) {
+        const size_t lo = c * kTokenChunk, hi = std::min(V, lo + kTokenChunk);
+        float mm = -inf;
+        for (size_t i = lo; i < hi; ++i) mm = y[i] > mm ? y[i] : mm;
+        mm = mm + 0.0f;
+        mc[c] = mm;
+        m = mm > m ? mm : m;
+        if (mm == -inf || mm == inf) continue;
+        float *lane = &lanes[c * 256];
+        for (size_t i = lo; i < hi; ++i) {
+            float &l = lane[((i - lo) / 4) % 256];
+            l = l + dllm::token::exp_le0(y[i] - mm);
+        }
+    }
+    if (m == -inf || m == inf) return;
+    float lane[256], tree[256];
+    for (float &l : lane) l = 0.0f;
+    for (size_t c = 0; c < C; ++c) {
+        if (mc[c] == -inf) {
+            w[c] = 0.0f;
+        } else {
+            std::memcpy(tree, &lanes[c * 256], sizeof(tree));
+            w[c] = tree256(tree) * dllm::token::exp_le0(mc[c] - m);
+        }
+        lane[c % 256] = lane[c % 256] + w[c];
+    }
+    const float Z = tree256(lane);
+    stats[0] = m;
+    stats[1] = Z;
+    // 5, 6. chunk, lane, element
+    const ptrdiff_t c = pick_host(w.data(), C, u[0]);
+    if (c < 0) return;
+    const ptrdiff_t j = pick_host(&lanes[static_cast<size_t>(c) * 256], 256, u[1]);
+    if (j < 0) return;
+    float e[64];
+    size_t at[64];
+    for (size_t q = 0; q < 64; ++q) {
+        at[q] = kTokenChunk * static_cast<size_t>(c) + 4 * (256 * (q / 4) + static_cast<size_t>(j)) + q % 4;
+        e[q] = at[q] < V ? dllm::token::exp_le0(y[at[q]] - mc[static_cast<size_t>(c)]) : 0.0f;
+    }
+    const ptrdiff_t q = pick_host(e, 64, u[2]);
+    if (q < 0) return;
+    // 7. the token and its probability
+    *token = static_cast<int32_t>(at[q]);
+    stats[2] = dllm::token::exp_le0(y[at[q]] - m) / Z;
 }
 
 #define STAGE_OK(s) \
@@ -413,6 +501,35 @@ int dllm_token_readout_host(const void *logits, int dtype, size_t M, size_t V, s
         const float m = stats[2 * b], Z = stats[2 * b + 1];
         const bool undefined = Z != Z || m == ninf;
         for (size_t i = 0; i < V; ++i) probs[b * V + i] = undefined ? qnan : dllm::token::exp_le0(x[i] - m) / Z;
+    }
+    return DLLM_OK;
+}
+
+int dllm_token_sample_host(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature,
+                           size_t top_k, const float *u, uint64_t seed, uint64_t offset, int32_t *tokens,
+                           float *stats) {
+    if (V == 0) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "V == 0: no token to sample from an empty vocabulary");
+    if (ld < V) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least V");
+    if (V >= (size_t(1) << 31))
+        return dllm::fail(DLLM_ERR_SHAPE_MISMATCH, "V must be below 2^31 (the token is an int32)");
+    if (dtype != DLLM_F32 && dtype != DLLM_F16)
+        return dllm::fail(DLLM_ERR_UNSUPPORTED, "dtype must be DLLM_F32 or DLLM_F16");
+    const float r = 1.0f / temperature;
+    if (!(temperature > 0.0f) || !std::isfinite(temperature) || !std::isfinite(r))
+        return dllm::fail(DLLM_ERR_INVALID_PARAMS, "temperature and 1 / temperature must be positive and finite");
+    if (M == 0) return DLLM_OK;
+    if (!logits || !tokens || !stats) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    std::vector<float> x(V), y(V);
+    for (size_t b = 0; b < M; ++b) {
+        for (size_t i = 0; i < V; ++i)
+            x[i] = dtype == DLLM_F16 ? half_bits_to_float(static_cast<const uint16_t *>(logits)[b * ld + i])
+                                     : static_cast<const float *>(logits)[b * ld + i];
+        float ub[3];
+        if (u)
+            std::memcpy(ub, u + 3 * b, sizeof(ub));
+        else
+            dllm::token::sample_uniforms(seed, offset + b, ub);
+        token_sample_row_host(x.data(), V, r, top_k, ub, y, tokens + b, stats + 3 * b);
     }
     return DLLM_OK;
 }

@@ -9,9 +9,15 @@
 //                        block reductions (last NaN + maximum; then sum + best), a piece per chunk
 //   token_row_kernel     one block per row: the pieces combined in order, Z through the same tree
 //   token_probs_kernel   p = EXP(x - m) / Z, elementwise, one block per (row, chunk)
-// No atomics, no allocation, no synchronisation.
+// and token sampling (8j): temperature, top-k and three seeded picks (chunk, lane, element) per row.
+//   token_select_kernel  one block per row, only when 0 < top_k < V: the threshold tau by a radix select
+//   token_chunk_kernel   the same kernel, its element transform y = RN(x r), -inf below tau
+//   token_pick_kernel    one block per row: the pieces combined, the chunk picked and read again, the
+//                        lane and the element picked, token and {m, Z, p_token} written
+// No global atomics, no allocation, no synchronisation.
 #include "common.hpp"
 #include "token_exp.hpp"
+#include "token_sample_rule.hpp"
 
 #include <limits>
 
@@ -117,13 +123,59 @@ __device__ __forceinline__ void tok_write_row(int32_t *tokens, float *stats, siz
     stats[2 * b + 1] = n >= 0 ? tok_nan() : Z;
 }
 
-// Block (b, c) = blockIdx.x: chunk c of row b -> part[b C + c]; for a one-chunk row, whose row
-// values are the piece's, tokens[b] and stats[b] directly.
+// The element transform of the chunk pass.  The readout reads the logits as they are; the sampler
+// (8j.1, 8j.2) reads y = RN(x r) with everything below the row's threshold tau turned into -inf
+// (tau == -inf masks nothing; a NaN compares false and stays a NaN).
+struct TokIdentity {
+    static constexpr bool kSample = false;
+    __device__ float tau(size_t) const { return 0.f; }
+    __device__ float operator()(float v, float) const { return v; }
+};
+struct TokTempered {
+    static constexpr bool kSample = true;
+    float r;
+    const float *taus;   // [M], or NULL when nothing is masked
+    __device__ float tau(size_t b) const { return taus ? taus[b] : tok_ninf(); }
+    __device__ float operator()(float v, float tau) const {
+        const float y = v * r;
+        return y < tau ? tok_ninf() : y;
+    }
+};
+
+template <typename Xf>
+__device__ __forceinline__ void tok_transform(float4 (&x)[kTokTrips], const Xf &xf, float tau) {
+#pragma unroll
+    for (int k = 0; k < kTokTrips; ++k) {
+        x[k].x = xf(x[k].x, tau);
+        x[k].y = xf(x[k].y, tau);
+        x[k].z = xf(x[k].z, tau);
+        x[k].w = xf(x[k].w, tau);
+    }
+}
+
+// The chunk of block-uniform index c of `row` in the lane's registers: all 16 loads in flight before
+// the first use; -inf at an index >= V.  (The pick pass's loads.  The chunk kernel spells the same two
+// loops out: through this helper hipcc emits another schedule for the identity instantiation than the
+// one the readout's record was measured with.)
 template <typename T>
+__device__ __forceinline__ void tok_load_chunk(float4 (&x)[kTokTrips], const T *__restrict__ row, size_t i0, bool full,
+                                               size_t V) {
+    if (full) {
+#pragma unroll
+        for (int k = 0; k < kTokTrips; ++k) x[k] = tok_load4(row + i0 + static_cast<size_t>(k) * (4 * kTokLanes));
+    } else {
+#pragma unroll
+        for (int k = 0; k < kTokTrips; ++k) x[k] = tok_group(row, i0 + static_cast<size_t>(k) * (4 * kTokLanes), V);
+    }
+}
+
+// Block (b, c) = blockIdx.x: chunk c of row b -> part[b C + c]; for a one-chunk row of the readout,
+// whose row values are the piece's, tokens[b] and stats[b] directly.
+template <typename T, typename Xf>
 __global__ void __launch_bounds__(kTokLanes) token_chunk_kernel(const T *__restrict__ logits, size_t V, size_t ld,
                                                                 size_t C, TokPiece *__restrict__ part,
                                                                 int32_t *__restrict__ tokens,
-                                                                float *__restrict__ stats) {
+                                                                float *__restrict__ stats, const Xf xf) {
     __shared__ float lds[kTokLanes];
     __shared__ float w_m[kTokWaves], w_bv[kTokWaves];
     __shared__ int w_n[kTokWaves], w_bi[kTokWaves], w_nan[kTokWaves];
@@ -143,6 +195,8 @@ __global__ void __launch_bounds__(kTokLanes) token_chunk_kernel(const T *__restr
 #pragma unroll
         for (int k = 0; k < kTokTrips; ++k) x[k] = tok_group(row, i0 + static_cast<size_t>(k) * (4 * kTokLanes), V);
     }
+
+    if constexpr (Xf::kSample) tok_transform(x, xf, xf.tau(b));
 
     // pass A: the maximum of the non-NaN elements, and whether there is a NaN at all
     float m = tok_ninf();
@@ -246,7 +300,7 @@ __global__ void __launch_bounds__(kTokLanes) token_chunk_kernel(const T *__restr
         float Z = s;
         if (m == tok_ninf()) Z = 0.f;
         if (n >= 0 || m == std::numeric_limits<float>::infinity()) Z = tok_nan();
-        if (C == 1) {
+        if (C == 1 && !Xf::kSample) {
             tok_write_row(tokens, stats, b, n, bi, m, Z);
         } else {
             TokPiece p;
@@ -341,6 +395,255 @@ __global__ void __launch_bounds__(kTokLanes) token_probs_kernel(const T *__restr
     }
 }
 
+// ---- token sampling (include/dllm_quant.h 8j) ------------------------------------------------------
+
+// The monotone u32 key of a non-NaN f32 (-0 counts as +0): a larger value has a larger key.
+__device__ __forceinline__ uint32_t tok_key(float y) {
+    uint32_t b = __float_as_uint(y);
+    b = b == 0x80000000u ? 0u : b;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float tok_unkey(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+constexpr int kSelBins = 2048;                          // 11 bits; the last pass uses the lower 1024
+constexpr int kSelThreads = 1024;
+constexpr int kSelWaves = kSelThreads / 64;
+constexpr int kSelCopies = 4;                           // copies of every bin, one per lane mod 4
+constexpr int kSelPer = kSelBins / kSelThreads;         // bins per thread in the rank search
+
+// Block b: taus[b] = the top_k-th largest y = RN(x r) of row b (0 < top_k < V), by a radix select on
+// the key: digits of 11, 11 and 10 bits from the top, one histogram in LDS per pass (integer atomics:
+// the counts do not depend on the order), the rank walked down from the largest digit.  The counts are
+// exact, so tau is the value 8j.2 defines whatever the order of arrival.  Logits crowd into a few
+// exponents, so the first digit's counts crowd into a few bins: every bin has four copies in adjacent
+// banks, lane l adds to copy l mod 4, and a wave's adds to one bin meet four at a time fewer.  A NaN's
+// key falls into some bin: such a row is degenerate whatever tau comes out.  Passes two and three
+// re-read the row (L2).
+template <typename T>
+__global__ void __launch_bounds__(kSelThreads) token_select_kernel(const T *__restrict__ logits, size_t V, size_t ld,
+                                                                   float r, uint32_t top_k, float *__restrict__ taus) {
+    __shared__ uint32_t hist[kSelBins * kSelCopies];
+    __shared__ uint32_t w_tot[kSelWaves];
+    __shared__ uint32_t sel[2];                          // the digit found, and the rank left inside it
+    const T *row = logits + blockIdx.x * ld;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid / 64;
+    uint32_t *mine = hist + (lane & (kSelCopies - 1));
+    uint32_t prefix = 0, himask = 0, k = top_k;
+    if (tid < 2) sel[tid] = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < 3; ++pass) {
+        const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0;
+        const uint32_t dmask = pass == 2 ? 1023u : 2047u;
+        for (int i = tid; i < kSelBins * kSelCopies; i += kSelThreads) hist[i] = 0;
+        __syncthreads();
+        const auto count = [&](float x) {
+            const uint32_t key = tok_key(x * r);
+            if ((key & himask) == prefix) atomicAdd(&mine[kSelCopies * ((key >> shift) & dmask)], 1u);
+        };
+        const auto count4 = [&](const float4 &v) { count(v.x), count(v.y), count(v.z), count(v.w); };
+        // the groups of four inside the row, four loads in flight; then the row's last one to three elements
+        const size_t G = V / 4;
+        size_t g = tid;
+        for (; g + 3 * kSelThreads < G; g += 4 * kSelThreads) {
+            float4 v[4];
+#pragma unroll
+            for (int n = 0; n < 4; ++n) v[n] = tok_load4(row + 4 * (g + static_cast<size_t>(n) * kSelThreads));
+#pragma unroll
+            for (int n = 0; n < 4; ++n) count4(v[n]);
+        }
+        for (; g < G; g += kSelThreads) count4(tok_load4(row + 4 * g));
+        if (4 * G + tid < V) count(tok_widen(row[4 * G + tid]));
+        __syncthreads();
+        // thread t owns bins 2047 - 2 t and 2046 - 2 t: an inclusive scan over t counts from the top
+        uint32_t cnt[kSelPer], ps = 0;
+#pragma unroll
+        for (int i = 0; i < kSelPer; ++i) {
+            const uint32_t *h = hist + kSelCopies * (kSelBins - 1 - (kSelPer * tid + i));
+            cnt[i] = h[0] + h[1] + h[2] + h[3];
+            ps += cnt[i];
+        }
+        uint32_t incl = ps;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t up = __shfl_up(incl, o, 64);
+            incl += lane >= o ? up : 0u;
+        }
+        if (lane == 63) w_tot[wave] = incl;
+        __syncthreads();
+        for (int w = 0; w < wave; ++w) incl += w_tot[w];
+        uint32_t above = incl - ps;
+        if (above < k && k <= incl) {                    // exactly one thread: the k-th largest lies in its bins
+#pragma unroll
+            for (int i = 0; i < kSelPer; ++i) {
+                if (above < k && k <= above + cnt[i]) {
+                    sel[0] = static_cast<uint32_t>(kSelBins - 1 - (kSelPer * tid + i));
+                    sel[1] = k - above;
+                }
+                above += cnt[i];
+            }
+        }
+        __syncthreads();
+        prefix |= sel[0] << shift;
+        himask |= dmask << shift;
+        k = sel[1];
+        __syncthreads();                                 // sel and hist are rewritten by the next pass
+    }
+    if (tid == 0) taus[blockIdx.x] = tok_unkey(prefix);
+}
+
+// Block b: row b's C pieces combined as token_row_kernel combines them (m; Z through lanes and tree),
+// then the three picks of 8j.6.  Level 1 is thread 0's fold over the C terms w_c (left in the pieces'
+// Z words).  The block then re-reads chunk c*, each lane rebuilding its sum with the adds of the chunk
+// pass; level 2 is thread 0's fold over the 256 lane sums, after which the one lane j whose prefix
+// F_j is the first above t knows it is j*; it does level 3 on its own registers and writes the token.
+template <typename T>
+__global__ void __launch_bounds__(kTokLanes) token_pick_kernel(const T *__restrict__ logits, size_t V, size_t ld, size_t C,
+                                                               TokPiece *__restrict__ part, const TokTempered xf,
+                                                               const float *__restrict__ u, uint64_t seed,
+                                                               uint64_t offset, int32_t *__restrict__ tokens,
+                                                               float *__restrict__ stats) {
+    __shared__ float lds[kTokLanes], fold[kTokLanes];
+    __shared__ float w_m[kTokWaves];
+    __shared__ int w_bad[kTokWaves];
+    __shared__ float sh_mc, sh_m, sh_Z, sh_u1, sh_u2;
+    __shared__ long long sh_c;
+    const size_t b = blockIdx.x;
+    TokPiece *P = part + b * C;
+    const int j = threadIdx.x;
+
+    float m = tok_ninf();
+    bool bad = false;                                    // a NaN in the row, or a chunk maximum of +inf
+    for (size_t c = j; c < C; c += kTokLanes) {
+        m = P[c].m > m ? P[c].m : m;
+        bad |= P[c].Z != P[c].Z;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64);
+        m = om > m ? om : m;
+    }
+    const int wave_bad = __any(bad);
+    if ((j & 63) == 0) {
+        w_m[j / 64] = m;
+        w_bad[j / 64] = wave_bad;
+    }
+    __syncthreads();
+    int row_bad = 0;
+#pragma unroll
+    for (int w = 0; w < kTokWaves; ++w) {
+        m = w_m[w] > m ? w_m[w] : m;
+        row_bad |= w_bad[w];
+    }
+    row_bad |= m == tok_ninf() || m == std::numeric_limits<float>::infinity();
+
+    float s = 0.f;
+    if (!row_bad)
+        for (size_t c = j; c < C; c += kTokLanes) {
+            const float mc = P[c].m;
+            const float w = mc == tok_ninf() ? 0.f : P[c].Z * token::exp_le0(mc - m);
+            P[c].Z = w;                                  // the term w_c, for level 1
+            s = s + w;
+        }
+    s = tok_tree(s, lds);                                // its barriers also publish the terms
+    if (j == 0) {
+        long long cs = -1;
+        if (row_bad) {
+            tokens[b] = -1;
+            stats[3 * b] = stats[3 * b + 1] = stats[3 * b + 2] = tok_nan();
+        } else {
+            float uu[3];
+            if (u) {
+                uu[0] = u[3 * b], uu[1] = u[3 * b + 1], uu[2] = u[3 * b + 2];
+            } else {
+                token::sample_uniforms(seed, offset + b, uu);
+            }
+            float S = 0.f;
+            for (size_t c = 0; c < C; ++c) S = S + P[c].Z;
+            const float t = uu[0] * S;
+            float F = 0.f;
+            for (size_t c = 0; c < C; ++c) {
+                F = F + P[c].Z;
+                if (t < F) {
+                    cs = static_cast<long long>(c);
+                    break;
+                }
+            }
+            stats[3 * b] = m;
+            stats[3 * b + 1] = s;
+            if (cs < 0) {
+                tokens[b] = -1;
+                stats[3 * b + 2] = tok_nan();
+            } else {
+                sh_mc = P[cs].m;
+                sh_m = m, sh_Z = s, sh_u1 = uu[1], sh_u2 = uu[2];
+            }
+        }
+        sh_c = cs;
+    }
+    __syncthreads();
+    if (sh_c < 0) return;                                // block-uniform
+    const size_t c = static_cast<size_t>(sh_c);
+    const float mc = sh_mc;
+
+    // chunk c* again: the lane sums, by the adds of the chunk pass (the row holds no NaN)
+    const T *row = logits + b * ld;
+    const size_t i0 = c * kTokChunk + 4 * static_cast<size_t>(j);
+    float4 x[kTokTrips];
+    tok_load_chunk(x, row, i0, (c + 1) * kTokChunk <= V, V);
+    const float tau = xf.tau(b);
+    tok_transform(x, xf, tau);
+    s = 0.f;
+#pragma unroll
+    for (int k = 0; k < kTokTrips; ++k) {                // the weights take the elements' registers
+        x[k].x = token::exp_le0_nonan(x[k].x - mc), s = s + x[k].x;
+        x[k].y = token::exp_le0_nonan(x[k].y - mc), s = s + x[k].y;
+        x[k].z = token::exp_le0_nonan(x[k].z - mc), s = s + x[k].z;
+        x[k].w = token::exp_le0_nonan(x[k].w - mc), s = s + x[k].w;
+    }
+    lds[j] = s;
+    __syncthreads();
+    if (j == 0) {
+        float F = 0.f;
+#pragma unroll 8
+        for (int i = 0; i < kTokLanes; ++i) {
+            F = F + lds[i];
+            fold[i] = F;
+        }
+    }
+    __syncthreads();
+    const float t2 = sh_u1 * fold[kTokLanes - 1];
+    if (j == 0 && !(t2 < fold[kTokLanes - 1])) {         // no lane qualifies
+        tokens[b] = -1;
+        stats[3 * b + 2] = tok_nan();
+    }
+    if (!(t2 < fold[j]) || (j > 0 && t2 < fold[j - 1])) return;   // the fold never decreases: one lane stays
+
+    // level 3, lane j*: its 64 elements in its own order, the fold being its own sum s
+    const float t3 = sh_u2 * s;
+    float F = 0.f;
+    int q = -1;
+#pragma unroll
+    for (int k = 0; k < kTokTrips; ++k) {
+        const float e[4] = {x[k].x, x[k].y, x[k].z, x[k].w};
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            F = F + e[l];
+            q = q < 0 && t3 < F ? 4 * k + l : q;
+        }
+    }
+    // an index >= V has weight +0 and is never picked: the token is below V < 2^31
+    const size_t tok = c * kTokChunk + 4 * (static_cast<size_t>(kTokLanes) * (q >> 2) + j) + (q & 3);
+    if (q < 0 || tok >= V) {
+        tokens[b] = -1;
+        stats[3 * b + 2] = tok_nan();
+    } else {
+        tokens[b] = static_cast<int32_t>(tok);
+        stats[3 * b + 2] = token::exp_le0_nonan(xf(tok_widen(row[tok]), tau) - sh_m) / sh_Z;
+    }
+}
+
 }  // namespace
 }  // namespace dllm
 
@@ -368,9 +671,11 @@ int dllm_token_readout(const void *logits, int dtype, size_t M, size_t V, size_t
     TokPiece *part = static_cast<TokPiece *>(workspace);
     hipStream_t st = as_stream(stream);
     if (dtype == DLLM_F16)
-        token_chunk_kernel<<<grid, kTokLanes, 0, st>>>(static_cast<const __half *>(logits), V, ld, C, part, tokens, stats);
+        token_chunk_kernel<<<grid, kTokLanes, 0, st>>>(static_cast<const __half *>(logits), V, ld, C, part, tokens, stats,
+                                                       TokIdentity{});
     else
-        token_chunk_kernel<<<grid, kTokLanes, 0, st>>>(static_cast<const float *>(logits), V, ld, C, part, tokens, stats);
+        token_chunk_kernel<<<grid, kTokLanes, 0, st>>>(static_cast<const float *>(logits), V, ld, C, part, tokens, stats,
+                                                       TokIdentity{});
     DLLM_LAUNCH_CHECK();
     if (C > 1) {
         token_row_kernel<<<static_cast<unsigned>(M), kTokLanes, 0, st>>>(part, C, tokens, stats);
@@ -383,6 +688,57 @@ int dllm_token_readout(const void *logits, int dtype, size_t M, size_t V, size_t
             token_probs_kernel<<<grid, kTokLanes, 0, st>>>(static_cast<const float *>(logits), V, ld, C, stats, probs);
         DLLM_LAUNCH_CHECK();
     }
+    return DLLM_OK;
+}
+
+size_t dllm_token_sample_workspace(size_t M, size_t V, size_t top_k) {
+    return M * tok_chunks(V) * sizeof(TokPiece) + (top_k > 0 && top_k < V ? M * sizeof(float) : 0);
+}
+
+int dllm_token_sample(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature, size_t top_k,
+                      const float *u, uint64_t seed, uint64_t offset, int32_t *tokens, float *stats, void *workspace,
+                      size_t workspace_bytes, dllm_stream_t stream) {
+    if (V == 0) return fail(DLLM_ERR_INVALID_PARAMS, "V == 0: no token to sample from an empty vocabulary");
+    if (ld < V) return fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least V");
+    if (V >= (size_t(1) << 31)) return fail(DLLM_ERR_SHAPE_MISMATCH, "V must be below 2^31 (the token is an int32)");
+    if (dtype != DLLM_F32 && dtype != DLLM_F16) return fail(DLLM_ERR_UNSUPPORTED, "dtype must be DLLM_F32 or DLLM_F16");
+    const float r = 1.0f / temperature;                 // 8j.1: one IEEE division
+    if (!(temperature > 0.0f) || !std::isfinite(temperature) || !std::isfinite(r))
+        return fail(DLLM_ERR_INVALID_PARAMS, "temperature and 1 / temperature must be positive and finite");
+    if (M == 0) return DLLM_OK;
+    if (!logits || !tokens || !stats || !workspace) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(workspace) % 4)
+        return fail(DLLM_ERR_INVALID_PARAMS, "workspace must be 4-byte aligned");
+    if (workspace_bytes < dllm_token_sample_workspace(M, V, top_k))
+        return fail(DLLM_ERR_INVALID_PARAMS, "workspace smaller than dllm_token_sample_workspace(M, V, top_k)");
+    const size_t C = tok_chunks(V);
+    if (C > 0x7fffffffu / M) return fail(DLLM_ERR_UNSUPPORTED, "M * ceil(V / 16384) exceeds the grid limit");
+    const unsigned grid = static_cast<unsigned>(M * C), rows = static_cast<unsigned>(M);
+    TokPiece *part = static_cast<TokPiece *>(workspace);
+    const bool masked = top_k > 0 && top_k < V;
+    float *taus = masked ? reinterpret_cast<float *>(part + M * C) : nullptr;
+    const TokTempered xf{r, taus};
+    hipStream_t st = as_stream(stream);
+    const bool f16 = dtype == DLLM_F16;
+    const __half *lh = static_cast<const __half *>(logits);
+    const float *lf = static_cast<const float *>(logits);
+    if (masked) {
+        if (f16)
+            token_select_kernel<<<rows, kSelThreads, 0, st>>>(lh, V, ld, r, static_cast<uint32_t>(top_k), taus);
+        else
+            token_select_kernel<<<rows, kSelThreads, 0, st>>>(lf, V, ld, r, static_cast<uint32_t>(top_k), taus);
+        DLLM_LAUNCH_CHECK();
+    }
+    if (f16)
+        token_chunk_kernel<<<grid, kTokLanes, 0, st>>>(lh, V, ld, C, part, tokens, stats, xf);
+    else
+        token_chunk_kernel<<<grid, kTokLanes, 0, st>>>(lf, V, ld, C, part, tokens, stats, xf);
+    DLLM_LAUNCH_CHECK();
+    if (f16)
+        token_pick_kernel<<<rows, kTokLanes, 0, st>>>(lh, V, ld, C, part, xf, u, seed, offset, tokens, stats);
+    else
+        token_pick_kernel<<<rows, kTokLanes, 0, st>>>(lf, V, ld, C, part, xf, u, seed, offset, tokens, stats);
+    DLLM_LAUNCH_CHECK();
     return DLLM_OK;
 }
 

@@ -3,7 +3,9 @@
 token (the reference's ``max_by`` fold, ties and NaNs included), stats = {m, Z} (the row maximum and
 the softmax denominator, so that the greedy token's probability is 1 / Z) and, on request, the
 probabilities -- tokens and stats from one read of the logits.  The rule is pinned in
-include/dllm_quant.h (section 8h) and is bit-reproducible on the host.
+include/dllm_quant.h (section 8h) and is bit-reproducible on the host.  ``sample_tokens`` is the
+sampling strategy the reference leaves open (section 8j): temperature, top-k and one seeded draw per
+row, pinned and reproducible in the same way.
 """
 from __future__ import annotations
 
@@ -26,12 +28,9 @@ def _workspace(device, nbytes):
     return ws
 
 
-def token_readout(logits: torch.Tensor, probs: bool = False):
-    """dllm_token_readout on logits [M, V] (f16 or f32; a 1-D tensor is one row) -> (tokens int32 [M],
-    stats f32 [M, 2] = {m, Z}), and with ``probs`` also the probabilities f32 [M, V].  Rows may be
-    strided (a column slice of a wider matrix is read in place); only the last dimension must be
-    dense.  A row holding a NaN gets stats {NaN, NaN}, a row of -inf {-inf, 0}; both keep their token
-    and touch no other row."""
+def _rows(logits):
+    """The layout handling of both entry points: logits as device rows [M, V] of f16 or f32 with a
+    dense last dimension -> (logits, single, M, V, ld)."""
     single = logits.dim() == 1
     if single:
         logits = logits.reshape(1, -1)
@@ -45,6 +44,16 @@ def token_readout(logits: torch.Tensor, probs: bool = False):
     if M and (logits.stride(1) != 1 or (M > 1 and logits.stride(0) < V)):
         logits = logits.contiguous()
     ld = int(logits.stride(0)) if M > 1 else V
+    return logits, single, M, V, ld
+
+
+def token_readout(logits: torch.Tensor, probs: bool = False):
+    """dllm_token_readout on logits [M, V] (f16 or f32; a 1-D tensor is one row) -> (tokens int32 [M],
+    stats f32 [M, 2] = {m, Z}), and with ``probs`` also the probabilities f32 [M, V].  Rows may be
+    strided (a column slice of a wider matrix is read in place); only the last dimension must be
+    dense.  A row holding a NaN gets stats {NaN, NaN}, a row of -inf {-inf, 0}; both keep their token
+    and touch no other row."""
+    logits, single, M, V, ld = _rows(logits)
     L = _lib.load()
     dev = logits.device
     tokens = torch.empty(M, dtype=torch.int32, device=dev)
@@ -57,6 +66,30 @@ def token_readout(logits: torch.Tensor, probs: bool = False):
     if single:
         tokens, stats, p = tokens[0], stats[0], (p[0] if probs else None)
     return (tokens, stats, p) if probs else (tokens, stats)
+
+
+def sample_tokens(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0, seed: int = 0, offset: int = 0,
+                  u: torch.Tensor = None):
+    """dllm_token_sample on logits [M, V] (layouts as ``token_readout``) -> (tokens int32 [M], stats f32
+    [M, 3] = {m, Z, p_token}): one token per row drawn from softmax(logits / temperature) restricted to
+    the ``top_k`` largest logits (0 = all; ties at the k-th place are all kept).  Row b draws with the
+    three uniforms of counter ``offset + b`` of the seeded stream ``seed``, or with ``u[b]`` (f32
+    [M, 3]) when ``u`` is given.  A row with a NaN or +inf, or of -inf, gets token -1 and NaN stats."""
+    logits, single, M, V, ld = _rows(logits)
+    if top_k < 0:
+        raise _lib.InvalidParams("top_k must not be negative")
+    L = _lib.load()
+    dev = logits.device
+    if u is not None:
+        u = u.to(device=dev, dtype=torch.float32).reshape(M, 3).contiguous()
+    tokens = torch.empty(M, dtype=torch.int32, device=dev)
+    stats = torch.empty(M, 3, dtype=torch.float32, device=dev)
+    wsb = L.dllm_token_sample_workspace(M, V, top_k)
+    ws = _workspace(dev, wsb)
+    check(L.dllm_token_sample(_ptr(logits), _lib.F16 if logits.dtype == torch.float16 else _lib.F32, M, V, ld,
+                              float(temperature), int(top_k), _ptr(u), seed & (2 ** 64 - 1), offset & (2 ** 64 - 1),
+                              _ptr(tokens), _ptr(stats), _ptr(ws), wsb, _stream()))
+    return (tokens[0], stats[0]) if single else (tokens, stats)
 
 
 class TokenHead:
@@ -79,6 +112,12 @@ class TokenHead:
         whose Z is 0: such a row has no distribution)."""
         tokens, stats = token_readout(self.logits(x))
         return tokens, 1.0 / stats[:, 1]
+
+    def sample(self, x: torch.Tensor, temperature: float = 1.0, top_k: int = 0, seed: int = 0,
+               offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """x [M, K] -> (tokens int32 [M], p_token f32 [M]): ``sample_tokens`` of the layer's logits."""
+        tokens, stats = sample_tokens(self.logits(x), temperature, top_k, seed, offset)
+        return tokens, stats[:, 2]
 
     def probabilities(self, x: torch.Tensor) -> torch.Tensor:
         """x [M, K] -> softmax over the vocabulary, f32 [M, V]."""

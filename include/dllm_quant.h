@@ -719,6 +719,67 @@ int dllm_dedup_rows(const uint64_t *hashes, size_t rows, uint64_t base, void *ta
 int dllm_gather_rows(const uint8_t *codes, size_t dim, size_t ld, const int32_t *kept_rows, const uint32_t *n_kept,
                      uint8_t *out, size_t out_ld, dllm_stream_t stream);
 
+/* ---- 8j token sampling: temperature, top-k and seeded draws over the vocabulary ---------------------
+ * sample_token (diffusion_prefill/src/lib.rs:162-174) is the greedy fold of 8h; its own comment says
+ * "in a real implementation, you'd use a sampling strategy".  This section is that strategy on device
+ * logits [M][V] (row stride ld >= V elements, f32, or f16 widened exactly): per row one token drawn
+ * from the tempered, top-k-masked softmax, and stats = {m, Z, p_token}.
+ *
+ * The rule (the contract: a row's outputs depend on that row's V elements, `temperature`, `top_k` and
+ * the row's three uniforms alone -- not on M, ld, the alignment, the grid or the device; nothing at or
+ * past index V of a row is ever read).
+ * 1. Temperature.  r = RN(1.0f / temperature), one IEEE division on the host; y_i = RN(x_i * r).
+ *    temperature == 1 gives y == x to the bit.
+ * 2. Top-k.  top_k == 0 or top_k >= V: nothing is masked.  Otherwise tau is the k-th largest y by value:
+ *    #{y_i > tau} < k <= #{y_i >= tau}, -0 equal to +0; every y_i with !(y_i >= tau) becomes -inf.
+ *    TIES AT tau ARE ALL KEPT: more than k elements may survive (k of a constant row keeps all V).  The
+ *    counts are integers, so no selection algorithm can change tau.
+ * 3. Row statistics.  Rules 8h.3 and 8h.4 on the masked y, unchanged: m_c, the lane sums s_j of
+ *    e = EXP(RN(y - m_c)), Z_c through the tree, the terms w_c = RN(Z_c EXP(RN(m_c - m))) (+0 when
+ *    m_c == -inf), Z through lanes and tree.  With temperature == 1 and top_k == 0, {m, Z} carry the bits
+ *    dllm_token_readout writes.  The kept maximum is never masked: Z >= 1 for a non-degenerate row.
+ * 4. Uniforms.  With u != NULL row b uses u[b][0..2].  Otherwise i = (offset + b) mod 2^64 and
+ *    (w0, w1, w2, w3) = Philox4x32-10 with key (seed lo, seed hi) on the counter (i lo, i hi, 1, 0); the 1
+ *    in the third word keeps these draws apart from the N(0,1) stream of 8f, whose counters are
+ *    (blk lo, blk hi, 0, 0).  u_l = float(w_l >> 8) * 2^-24, exact, in [0, 1 - 2^-24]; w3 is unused.
+ *    There is no alignment condition on offset.
+ * 5. Pick.  For weights a_0 .. a_{n-1} >= +0 and a uniform v: F_j = RN(F_{j-1} + a_j) is the sequential
+ *    f32 fold from +0, S = F_{n-1}, t = RN(v S); the pick is the first j with t < F_j.  For v in
+ *    [0, 1 - 2^-24] and S > 0, t < S always holds (S 2^-24 is at least half an ulp of S, so S (1 - 2^-24) lies
+ *    below the midpoint between pred(S) and S -- or, when S is a power of two, is pred(S) itself -- and
+ *    rounds to pred(S) at most), so a pick exists; it never lands on a zero weight,
+ *    because F_j > F_{j-1} needs a_j > 0.  If no j qualifies -- a caller-supplied v outside [0, 1), or a
+ *    NaN -- the row's token is -1 and p_token the quiet NaN (m and Z are still written).
+ * 6. Three levels, one uniform each.  Chunk c* = pick over w_0 .. w_{C-1} with u_0.  Lane j* = pick over
+ *    chunk c*'s 256 lane sums s_0 .. s_255 (the values before the tree) with u_1.  Element = pick with u_2
+ *    over lane j*'s 64 elements in the lane's own order (trips g' = 0 .. 15, components 0 .. 3): element
+ *    q = 4 g' + comp has row index 16384 c* + 4 (256 g' + j*) + comp and weight EXP(RN(y - m_c*)), +0 at
+ *    an index >= V; its fold is the lane's own sum, S = s_j*.  The product of the three conditional
+ *    probabilities is e_i EXP(m_c - m) / Z up to rounding: the rule samples the tempered, masked softmax.
+ * 7. p_token = RN(EXP(RN(y_tok - m)) / Z), as 8h.5.
+ * 8. Degenerate rows.  A NaN in the row, m == +inf (which includes x r overflowing) or m == -inf give
+ *    token -1 and stats = {NaN, NaN, NaN} (0x7fc00000), whatever tau is.  Such a row touches no other row.
+ * Bound: {m, Z} and p_token carry 8h's bound, with y for x.  Each level's conditional probability
+ * differs from a_j / sum a by the fold's rounding, at most n u relative (n = C, 256, 64; u = 2^-24).
+ * Checks, in this order, before anything touches the device:
+ * V == 0 or ld < V -> INVALID_PARAMS; V >= 2^31 -> SHAPE_MISMATCH; a dtype other than DLLM_F32 /
+ * DLLM_F16 -> UNSUPPORTED; !(temperature > 0), or temperature or r not finite -> INVALID_PARAMS;
+ * M == 0 -> DLLM_OK, nothing written; a NULL logits, tokens, stats or workspace, a workspace not 4-byte
+ * aligned or shorter than dllm_token_sample_workspace(M, V, top_k) -> INVALID_PARAMS.
+ * (M ceil(V / 16384) >= 2^31 -> UNSUPPORTED: the grid.) */
+/* Bytes of device workspace dllm_token_sample needs: the chunk pieces, M * ceil(V / 16384) * 20, and,
+ * when 0 < top_k < V, the rows' thresholds, M * 4. */
+size_t dllm_token_sample_workspace(size_t M, size_t V, size_t top_k);
+/* tokens (device i32 [M]) and stats (device f32 [M][3] = {m, Z, p_token}) of logits (device, as
+ * dllm_token_readout's: any alignment and any ld give the same bits).  u: device f32 [M][3], or NULL
+ * for the seeded stream.  Asynchronous on `stream`; never synchronises or allocates (graph-capturable
+ * from the first call); no global atomics (the threshold search counts in LDS with integer atomics,
+ * whose result is order-free). */
+int dllm_token_sample(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature,
+                      size_t top_k, const float *u /* device [M][3] or NULL */, uint64_t seed, uint64_t offset,
+                      int32_t *tokens /* [M] */, float *stats /* [M][3] */, void *workspace,
+                      size_t workspace_bytes, dllm_stream_t stream);
+
 /* ---- host-slice variants (synchronous; stage through device memory; not graph-capturable) ----
  * The literal shapes of the reference's Rust signatures, for callers holding host slices. */
 /* quantize_tensor(&[f32], u8) -> (Vec<u8>, f32, f32): codes one per byte (quantization.rs:38-68). */
@@ -754,6 +815,11 @@ int dllm_search_vectors_host(const float *Q, size_t nq, const uint8_t *codes, co
  * workspace), the same bits as the kernels; the same checks and codes. */
 int dllm_token_readout_host(const void *logits, int dtype, size_t M, size_t V, size_t ld, int32_t *tokens,
                             float *stats /* [M][2] */, float *probs /* [M][V] or NULL */);
+/* dllm_token_sample on host slices (u a host array or NULL): the rule of section 8j in plain C++ (no
+ * device, no staging, no workspace), the same bits as the kernels; the same checks and codes. */
+int dllm_token_sample_host(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature,
+                           size_t top_k, const float *u /* [M][3] or NULL */, uint64_t seed, uint64_t offset,
+                           int32_t *tokens /* [M] */, float *stats /* [M][3] */);
 /* Section 8i on host slices: serial restatements of the reference's loops in plain C++ (no device,
  * no staging, no workspace), the same bits as the kernels; the same checks and codes, minus the
  * workspace's.  The seen-set is host memory of the same size and layout (dllm_dedup_table_bytes,
