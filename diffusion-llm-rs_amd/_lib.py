@@ -167,6 +167,9 @@ SIGNATURES = {
     "dllm_token_sample_workspace": (S, [S, S, S]),
     "dllm_token_sample": (INT, [P, INT, S, S, S, FL, S, P, U64, U64, P, P, P, S, P]),
     "dllm_token_sample_host": (INT, [P, INT, S, S, S, FL, S, P, U64, U64, P, P]),
+    "dllm_token_sample_ex_workspace": (S, [S, S, S, FL, FL]),
+    "dllm_token_sample_ex": (INT, [P, INT, S, S, S, FL, S, FL, FL, P, U64, U64, P, P, P, S, P]),
+    "dllm_token_sample_ex_host": (INT, [P, INT, S, S, S, FL, S, FL, FL, P, U64, U64, P, P]),
     "dllm_hash_rows": (INT, [P, S, S, S, P, P]),
     "dllm_dedup_table_bytes": (S, [S]),
     "dllm_dedup_table_init": (INT, [P, S, P]),

@@ -15,6 +15,7 @@
 #include "dedup_rule.hpp"
 #include "dllm_quant.h"
 #include "token_exp.hpp"
+#include "token_nucleus_rule.hpp"
 #include "token_sample_rule.hpp"
 
 namespace dllm {
@@ -202,12 +203,60 @@ ptrdiff_t pick_host(const float *a, size_t n, float v) {
     return -1;
 }
 
-// One row of V widened logits -> token, {m, Z, p_token}.  y is scratch of V floats.
+// The masks of 8k in fixed point; off = {1 << 32 (top_p == 1), 0}.
+struct NucleusParams {
+    bool p_on;
+    uint64_t pfix, mfix;
+};
+
+// 8k.2 - 8k.4 on a row without a NaN: the larger of tau_p and tau_m (-inf when both masks are off).
+// tau_k is the top-k threshold (-inf when off).  Literally the rule: the weights, then a walk down the
+// sorted row for top-p and a minimum over the qualifying set for min-p.
+float nucleus_tau_host(const std::vector<float> &y, size_t V, float tau_k, const NucleusParams &np) {
+    const float inf = std::numeric_limits<float>::infinity();
+    float m = -inf;
+    for (size_t i = 0; i < V; ++i) m = y[i] > m ? y[i] : m;
+    m = m + 0.0f;
+    if (m == -inf || m == inf) return -inf;             // degenerate: the caller reports NaN
+    std::vector<std::pair<float, uint64_t>> e(V);
+    uint64_t T = 0;
+    for (size_t i = 0; i < V; ++i) {
+        const uint64_t W = y[i] >= tau_k ? dllm::token::nucleus_weight(dllm::token::exp_le0(y[i] - m)) : 0;
+        e[i] = {y[i], W};
+        T += W;
+    }
+    float tau = -inf;
+    if (np.p_on) {
+        std::sort(e.begin(), e.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
+        uint64_t A = 0;
+        for (size_t i = 0; i < V;) {                    // one distinct value (-0 == +0) per trip
+            size_t j = i;
+            for (; j < V && e[j].first == e[i].first; ++j) A += e[j].second;
+            if ((static_cast<unsigned __int128>(A) << 32) >= static_cast<unsigned __int128>(np.pfix) * T) {
+                tau = e[i].first;
+                break;
+            }
+            i = j;
+        }
+    }
+    if (np.mfix) {
+        float tm = inf;
+        for (size_t i = 0; i < V; ++i)
+            if (e[i].second >= np.mfix && e[i].first < tm) tm = e[i].first;
+        tau = tm > tau ? tm : tau;
+    }
+    return tau;
+}
+
+// One row of V widened logits -> token, {m, Z, p_token} and, with tau_out, the threshold of 8k.5.
+// y is scratch of V floats.
 void token_sample_row_host(const float *x, size_t V, float r, size_t top_k, const float *u, std::vector<float> &y,
-                           int32_t *token, float *stats) {
+                           int32_t *token, float *stats, const NucleusParams &np = {false, 0, 0},
+                           float *tau_out = nullptr) {
     const float inf = std::numeric_limits<float>::infinity(), qnan = dllm::token::exp_le0(std::nanf(""));
     *token = -1;
     stats[0] = stats[1] = stats[2] = qnan;
+    if (tau_out) *tau_out = qnan;
     // 1. temperature
     bool nan = false;
     for (size_t i = 0; i < V; ++i) {
@@ -215,14 +264,21 @@ void token_sample_row_host(const float *x, size_t V, float r, size_t top_k, cons
         nan |= y[i] != y[i];
     }
     if (nan) return;
-    // 2. top-k: tau = the k-th largest value; everything below it becomes -inf
+    // 2. top-k: tau = the k-th largest value; then 8k's thresholds; everything below becomes -inf
+    float tau = -inf;
     if (top_k > 0 && top_k < V) {
         std::vector<float> v(y.begin(), y.end());
         std::nth_element(v.begin(), v.begin() + static_cast<ptrdiff_t>(top_k - 1), v.end(), std::greater<float>());
-        const float tau = v[top_k - 1];
+        tau = v[top_k - 1];
+    }
+    if (np.p_on || np.mfix) {
+        const float t = nucleus_tau_host(y, V, tau, np);
+        tau = t > tau ? t : tau;
+    }
+    tau = tau + 0.0f;                                    // a zero threshold is +0
+    if (tau != -inf)
         for (size_t i = 0; i < V; ++i)
             if (!(y[i] >= tau)) y[i] = -inf;
-    }
     // 3. chunk partials and the row, as 8h.3 and 8h.4 (the lane sums are kept: level 2 picks among them)
     const size_t C = (V + kTokenChunk - 1) / kTokenChunk;
     std::vector<float> mc(C), w(C), lanes(C * 256, 0.0f);
@@ -242,6 +298,7 @@ void token_sample_row_host(const float *x, size_t V, float r, size_t top_k, cons
         }
     }
     if (m == -inf || m == inf) return;
+    if (tau_out) *tau_out = tau;
     float lane[256], tree[256];
     for (float &l : lane) l = 0.0f;
     for (size_t c = 0; c < C; ++c) {
@@ -530,6 +587,39 @@ int dllm_token_sample_host(const void *logits, int dtype, size_t M, size_t V, si
         else
             dllm::token::sample_uniforms(seed, offset + b, ub);
         token_sample_row_host(x.data(), V, r, top_k, ub, y, tokens + b, stats + 3 * b);
+    }
+    return DLLM_OK;
+}
+
+int dllm_token_sample_ex_host(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature,
+                              size_t top_k, float top_p, float min_p, const float *u, uint64_t seed, uint64_t offset,
+                              int32_t *tokens, float *stats) {
+    if (V == 0) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "V == 0: no token to sample from an empty vocabulary");
+    if (ld < V) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least V");
+    if (V >= (size_t(1) << 31))
+        return dllm::fail(DLLM_ERR_SHAPE_MISMATCH, "V must be below 2^31 (the token is an int32)");
+    if (dtype != DLLM_F32 && dtype != DLLM_F16)
+        return dllm::fail(DLLM_ERR_UNSUPPORTED, "dtype must be DLLM_F32 or DLLM_F16");
+    const float r = 1.0f / temperature;
+    if (!(temperature > 0.0f) || !std::isfinite(temperature) || !std::isfinite(r))
+        return dllm::fail(DLLM_ERR_INVALID_PARAMS, "temperature and 1 / temperature must be positive and finite");
+    if (!(top_p > 0.0f) || top_p > 1.0f) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "top_p must be in (0, 1]");
+    if (!(min_p >= 0.0f) || min_p > 1.0f) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "min_p must be in [0, 1]");
+    if (M == 0) return DLLM_OK;
+    if (!logits || !tokens || !stats) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    const NucleusParams np{top_p != 1.0f, dllm::token::nucleus_pfix(top_p), dllm::token::nucleus_mfix(min_p)};
+    std::vector<float> x(V), y(V);
+    for (size_t b = 0; b < M; ++b) {
+        for (size_t i = 0; i < V; ++i)
+            x[i] = dtype == DLLM_F16 ? half_bits_to_float(static_cast<const uint16_t *>(logits)[b * ld + i])
+                                     : static_cast<const float *>(logits)[b * ld + i];
+        float ub[3], st[3];
+        if (u)
+            std::memcpy(ub, u + 3 * b, sizeof(ub));
+        else
+            dllm::token::sample_uniforms(seed, offset + b, ub);
+        token_sample_row_host(x.data(), V, r, top_k, ub, y, tokens + b, st, np, stats + 4 * b + 3);
+        std::memcpy(stats + 4 * b, st, sizeof(st));
     }
     return DLLM_OK;
 }

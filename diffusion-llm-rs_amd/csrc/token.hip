@@ -14,9 +14,13 @@
 //   token_chunk_kernel   the same kernel, its element transform y = RN(x r), -inf below tau
 //   token_pick_kernel    one block per row: the pieces combined, the chunk picked and read again, the
 //                        lane and the element picked, token and {m, Z, p_token} written
+// Top-p and min-p (8k) are one more question about the same threshold:
+//   token_nucleus_kernel one block per row, only when top_p < 1 or min_p > 0, after the select: m, then a
+//                        radix select over u64 weight sums; the combined tau replaces the select's
 // No global atomics, no allocation, no synchronisation.
 #include "common.hpp"
 #include "token_exp.hpp"
+#include "token_nucleus_rule.hpp"
 #include "token_sample_rule.hpp"
 
 #include <limits>
@@ -493,12 +497,191 @@ __global__ void __launch_bounds__(kSelThreads) token_select_kernel(const T *__re
     if (tid == 0) taus[blockIdx.x] = tok_unkey(prefix);
 }
 
+// ---- top-p and min-p (include/dllm_quant.h 8k) -----------------------------------------------------
+
+constexpr int kNucBins = 2048;                          // 11 bits; the last pass uses the lower 1024
+constexpr int kNucThreads = 1024;
+constexpr int kNucWaves = kNucThreads / 64;
+constexpr int kNucCopies = 4;                           // copies of every bin, one per lane mod 4
+constexpr int kNucPer = kNucBins / kNucThreads;         // bins per thread in the walk
+constexpr uint32_t kNucKeyNinf = 0x007fffffu;           // tok_key(-inf): below the key of every other non-NaN value
+
+// f(v) for every group of four of the row, each exactly once, two loads in flight; the elements of the
+// last group that lie at or past V are -inf and are never read.  The trip counts depend on V alone.
+template <typename T, typename F>
+__device__ __forceinline__ void nuc_for_each(const T *__restrict__ row, size_t V, int tid, const F &f) {
+    constexpr size_t step = 4 * kNucThreads;
+    size_t i = 4 * static_cast<size_t>(tid);
+    for (; i + step + 4 <= V; i += 2 * step) {
+        const float4 a = tok_load4(row + i), b = tok_load4(row + i + step);
+        f(a);
+        f(b);
+    }
+    for (; i < V; i += step) f(tok_group(row, i, V));   // at most two trips
+}
+
+// Block b: the combined threshold of 8k.5 into taus[b], which on entry holds the top-k threshold of
+// token_select_kernel when has_k (else nothing).  One read of the row for m (and whether the row is
+// degenerate); then, when top-p is on, a radix select on the key of y as in token_select_kernel --
+// digits of 11, 11 and 10 bits from the top -- whose bins hold u64 sums of the weights W (8k.2) instead
+// of counts: integer LDS atomics, so a bin's sum does not depend on the order of arrival.  The bins are
+// walked from the largest digit until the mass reaches `need` (token_nucleus_rule.hpp: the 96-bit
+// comparison of 8k.3 folded into one u64 per row); a bin of weight 0 never decides, so the value found
+// is one of the row's.  The first pass pays EXP for every element and also yields T (the walk's grand
+// total) and the min-p minimum; the later passes pay it only for elements under the prefix found so
+// far.  Four copies of every bin, one per lane mod 4, as in the select: 64 KiB of LDS, two blocks per
+// CU, which is the CU's 32 waves (8 per SIMD: the launch bound asks for the 64 VGPRs that takes).
+// A degenerate row (a NaN, m = +-inf) runs the same passes, adds nothing to any bin and ends with
+// tau = -inf: no trip count depends on the data.
+template <typename T>
+__global__ void __launch_bounds__(kNucThreads, 8) token_nucleus_kernel(const T *__restrict__ logits, size_t V, size_t ld,
+                                                                    float r, int has_k, int p_on, uint64_t pfix,
+                                                                    uint64_t mfix, float *__restrict__ taus) {
+    __shared__ unsigned long long hist[kNucBins * kNucCopies];
+    __shared__ unsigned long long w_tot[kNucWaves];
+    __shared__ unsigned long long sel_rem;               // the mass still to reach inside the digit found
+    __shared__ uint32_t sel_bin;                         // the digit found
+    __shared__ float w_m[kNucWaves];
+    __shared__ int w_nan[kNucWaves];
+    __shared__ uint32_t w_min[kNucWaves];
+    const T *row = logits + blockIdx.x * ld;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid / 64;
+
+    // the row maximum of y = RN(x r) over the non-NaN elements, and whether there is a NaN
+    float m = tok_ninf();
+    bool nan = false;
+    nuc_for_each(row, V, tid, [&](const float4 &v) {
+        const float y[4] = {v.x * r, v.y * r, v.z * r, v.w * r};
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            nan |= y[l] != y[l];
+            m = y[l] > m ? y[l] : m;
+        }
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64);
+        m = om > m ? om : m;
+    }
+    const int wave_nan = __any(nan);
+    if (lane == 0) {
+        w_m[wave] = m;
+        w_nan[wave] = wave_nan;
+    }
+    if (tid == 0) {
+        sel_bin = 0;
+        sel_rem = 0;
+    }
+    __syncthreads();
+    int any_nan = 0;
+#pragma unroll
+    for (int w = 0; w < kNucWaves; ++w) {
+        m = w_m[w] > m ? w_m[w] : m;
+        any_nan |= w_nan[w];
+    }
+    m = m + 0.0f;
+    const bool ok = !any_nan && m != tok_ninf() && m != std::numeric_limits<float>::infinity();
+    const float tau_k = has_k ? taus[blockIdx.x] : tok_ninf();
+
+    unsigned long long *mine = hist + (lane & (kNucCopies - 1));
+    uint32_t prefix = 0, himask = 0, minkey = 0xffffffffu;
+    unsigned long long need = 0;
+    // unrolled: inside a rolled loop hipcc keeps the loop-invariant addresses, shuffle offsets and EXP
+    // constants of all passes in registers (89 VGPRs, one block per CU); unrolled it takes 51-53
+#pragma unroll
+    for (int pass = 0; pass < 3; ++pass) {
+        const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0;
+        const uint32_t dmask = pass == 2 ? 1023u : 2047u;
+        if (p_on) {
+            for (int i = tid; i < kNucBins * kNucCopies; i += kNucThreads) hist[i] = 0;
+            __syncthreads();
+        }
+        nuc_for_each(row, V, tid, [&](const float4 &v) {
+            const float y[4] = {v.x * r, v.y * r, v.z * r, v.w * r};
+            uint32_t key[4];
+            bool live[4];
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                key[l] = tok_key(y[l]);
+                live[l] = ok && (key[l] & himask) == prefix && y[l] >= tau_k;   // !ok is block-uniform
+            }
+            if (!(live[0] || live[1] || live[2] || live[3])) return;   // EXP only under the prefix found so far
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                const float g = token::exp_le0_nonan(live[l] ? y[l] - m : tok_ninf());
+                const unsigned long long W = token::nucleus_weight(g);   // 0 for an element that is not live
+                minkey = mfix && W >= mfix && key[l] < minkey ? key[l] : minkey;
+                if (p_on && W) atomicAdd(&mine[kNucCopies * ((key[l] >> shift) & dmask)], W);
+            }
+        });
+        if (!p_on) break;                                // min-p alone: one pass, no histogram
+        __syncthreads();
+        // thread t owns bins 2047 - 2 t and 2046 - 2 t: an inclusive scan over t sums from the top
+        unsigned long long sum[kNucPer], ps = 0;
+#pragma unroll
+        for (int i = 0; i < kNucPer; ++i) {
+            const unsigned long long *h = hist + kNucCopies * (kNucBins - 1 - (kNucPer * tid + i));
+            sum[i] = h[0] + h[1] + h[2] + h[3];
+            ps += sum[i];
+        }
+        unsigned long long incl = ps;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long up = __shfl_up(incl, o, 64);
+            incl += lane >= o ? up : 0ull;
+        }
+        if (lane == 63) w_tot[wave] = incl;
+        __syncthreads();
+        unsigned long long total = 0;
+#pragma unroll
+        for (int w = 0; w < kNucWaves; ++w) {
+            incl += w < wave ? w_tot[w] : 0ull;
+            total += w_tot[w];
+        }
+        if (pass == 0) need = token::nucleus_need(pfix, total);   // total is T: every element took part
+        unsigned long long above = incl - ps;
+        if (above < need && need <= incl) {              // exactly one thread: the mass is reached in its bins
+#pragma unroll
+            for (int i = 0; i < kNucPer; ++i) {
+                if (above < need && need <= above + sum[i]) {
+                    sel_bin = static_cast<uint32_t>(kNucBins - 1 - (kNucPer * tid + i));
+                    sel_rem = need - above;
+                }
+                above += sum[i];
+            }
+        }
+        __syncthreads();
+        prefix |= sel_bin << shift;
+        himask |= dmask << shift;
+        need = sel_rem;
+        __syncthreads();                                 // sel_* and hist are rewritten by the next pass
+    }
+
+    // the min-p minimum over the block (the first pass saw every element)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t ok_ = __shfl_xor(minkey, o, 64);
+        minkey = ok_ < minkey ? ok_ : minkey;
+    }
+    if (lane == 0) w_min[wave] = minkey;
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 0; w < kNucWaves; ++w) minkey = w_min[w] < minkey ? w_min[w] : minkey;
+        uint32_t key = has_k ? tok_key(tau_k) : kNucKeyNinf;
+        if (p_on) key = prefix > key ? prefix : key;
+        if (mfix) key = minkey > key ? minkey : key;
+        taus[blockIdx.x] = ok ? tok_unkey(key) : tok_ninf();
+    }
+}
+
 // Block b: row b's C pieces combined as token_row_kernel combines them (m; Z through lanes and tree),
 // then the three picks of 8j.6.  Level 1 is thread 0's fold over the C terms w_c (left in the pieces'
 // Z words).  The block then re-reads chunk c*, each lane rebuilding its sum with the adds of the chunk
 // pass; level 2 is thread 0's fold over the 256 lane sums, after which the one lane j whose prefix
 // F_j is the first above t knows it is j*; it does level 3 on its own registers and writes the token.
-template <typename T>
+// kStats is the width of a stats row: 3 = {m, Z, p_token} (8j), 4 adds the row's threshold tau (8k).
+template <typename T, int kStats>
 __global__ void __launch_bounds__(kTokLanes) token_pick_kernel(const T *__restrict__ logits, size_t V, size_t ld, size_t C,
                                                                TokPiece *__restrict__ part, const TokTempered xf,
                                                                const float *__restrict__ u, uint64_t seed,
@@ -549,9 +732,10 @@ __global__ void __launch_bounds__(kTokLanes) token_pick_kernel(const T *__restri
     s = tok_tree(s, lds);                                // its barriers also publish the terms
     if (j == 0) {
         long long cs = -1;
+        if constexpr (kStats == 4) stats[kStats * b + 3] = row_bad ? tok_nan() : xf.tau(b);
         if (row_bad) {
             tokens[b] = -1;
-            stats[3 * b] = stats[3 * b + 1] = stats[3 * b + 2] = tok_nan();
+            stats[kStats * b] = stats[kStats * b + 1] = stats[kStats * b + 2] = tok_nan();
         } else {
             float uu[3];
             if (u) {
@@ -570,11 +754,11 @@ __global__ void __launch_bounds__(kTokLanes) token_pick_kernel(const T *__restri
                     break;
                 }
             }
-            stats[3 * b] = m;
-            stats[3 * b + 1] = s;
+            stats[kStats * b] = m;
+            stats[kStats * b + 1] = s;
             if (cs < 0) {
                 tokens[b] = -1;
-                stats[3 * b + 2] = tok_nan();
+                stats[kStats * b + 2] = tok_nan();
             } else {
                 sh_mc = P[cs].m;
                 sh_m = m, sh_Z = s, sh_u1 = uu[1], sh_u2 = uu[2];
@@ -616,7 +800,7 @@ __global__ void __launch_bounds__(kTokLanes) token_pick_kernel(const T *__restri
     const float t2 = sh_u1 * fold[kTokLanes - 1];
     if (j == 0 && !(t2 < fold[kTokLanes - 1])) {         // no lane qualifies
         tokens[b] = -1;
-        stats[3 * b + 2] = tok_nan();
+        stats[kStats * b + 2] = tok_nan();
     }
     if (!(t2 < fold[j]) || (j > 0 && t2 < fold[j - 1])) return;   // the fold never decreases: one lane stays
 
@@ -637,10 +821,10 @@ __global__ void __launch_bounds__(kTokLanes) token_pick_kernel(const T *__restri
     const size_t tok = c * kTokChunk + 4 * (static_cast<size_t>(kTokLanes) * (q >> 2) + j) + (q & 3);
     if (q < 0 || tok >= V) {
         tokens[b] = -1;
-        stats[3 * b + 2] = tok_nan();
+        stats[kStats * b + 2] = tok_nan();
     } else {
         tokens[b] = static_cast<int32_t>(tok);
-        stats[3 * b + 2] = token::exp_le0_nonan(xf(tok_widen(row[tok]), tau) - sh_m) / sh_Z;
+        stats[kStats * b + 2] = token::exp_le0_nonan(xf(tok_widen(row[tok]), tau) - sh_m) / sh_Z;
     }
 }
 
@@ -695,6 +879,63 @@ size_t dllm_token_sample_workspace(size_t M, size_t V, size_t top_k) {
     return M * tok_chunks(V) * sizeof(TokPiece) + (top_k > 0 && top_k < V ? M * sizeof(float) : 0);
 }
 
+size_t dllm_token_sample_ex_workspace(size_t M, size_t V, size_t top_k, float top_p, float min_p) {
+    const bool slot = (top_k > 0 && top_k < V) || top_p != 1.0f || min_p != 0.0f;
+    return M * tok_chunks(V) * sizeof(TokPiece) + (slot ? M * sizeof(float) : 0);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The launches of both sampling entry points, after their checks.  kStats = 3 is dllm_token_sample;
+// kStats = 4 is dllm_token_sample_ex, whose threshold search runs between the select and the chunk pass
+// when a mask of 8k is on (nucleus) and leaves the combined tau in the select's slot.
+template <int kStats>
+int token_sample_launch(const void *logits, int dtype, size_t M, size_t V, size_t ld, float r, size_t top_k, bool p_on,
+                        uint64_t pfix, uint64_t mfix, const float *u, uint64_t seed, uint64_t offset, int32_t *tokens,
+                        float *stats, void *workspace, dllm_stream_t stream) {
+    const size_t C = tok_chunks(V);
+    const unsigned grid = static_cast<unsigned>(M * C), rows = static_cast<unsigned>(M);
+    TokPiece *part = static_cast<TokPiece *>(workspace);
+    const bool masked = top_k > 0 && top_k < V, nucleus = p_on || mfix != 0;
+    float *taus = masked || nucleus ? reinterpret_cast<float *>(part + M * C) : nullptr;
+    const TokTempered xf{r, taus};
+    hipStream_t st = as_stream(stream);
+    const bool f16 = dtype == DLLM_F16;
+    const __half *lh = static_cast<const __half *>(logits);
+    const float *lf = static_cast<const float *>(logits);
+    if (masked) {
+        if (f16)
+            token_select_kernel<<<rows, kSelThreads, 0, st>>>(lh, V, ld, r, static_cast<uint32_t>(top_k), taus);
+        else
+            token_select_kernel<<<rows, kSelThreads, 0, st>>>(lf, V, ld, r, static_cast<uint32_t>(top_k), taus);
+        DLLM_LAUNCH_CHECK();
+    }
+    if (nucleus) {
+        if (f16)
+            token_nucleus_kernel<<<rows, kNucThreads, 0, st>>>(lh, V, ld, r, masked, p_on, pfix, mfix, taus);
+        else
+            token_nucleus_kernel<<<rows, kNucThreads, 0, st>>>(lf, V, ld, r, masked, p_on, pfix, mfix, taus);
+        DLLM_LAUNCH_CHECK();
+    }
+    if (f16)
+        token_chunk_kernel<<<grid, kTokLanes, 0, st>>>(lh, V, ld, C, part, tokens, stats, xf);
+    else
+        token_chunk_kernel<<<grid, kTokLanes, 0, st>>>(lf, V, ld, C, part, tokens, stats, xf);
+    DLLM_LAUNCH_CHECK();
+    if (f16)
+        token_pick_kernel<__half, kStats><<<rows, kTokLanes, 0, st>>>(lh, V, ld, C, part, xf, u, seed, offset, tokens, stats);
+    else
+        token_pick_kernel<float, kStats><<<rows, kTokLanes, 0, st>>>(lf, V, ld, C, part, xf, u, seed, offset, tokens, stats);
+    DLLM_LAUNCH_CHECK();
+    return DLLM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int dllm_token_sample(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature, size_t top_k,
                       const float *u, uint64_t seed, uint64_t offset, int32_t *tokens, float *stats, void *workspace,
                       size_t workspace_bytes, dllm_stream_t stream) {
@@ -711,35 +952,33 @@ int dllm_token_sample(const void *logits, int dtype, size_t M, size_t V, size_t 
         return fail(DLLM_ERR_INVALID_PARAMS, "workspace must be 4-byte aligned");
     if (workspace_bytes < dllm_token_sample_workspace(M, V, top_k))
         return fail(DLLM_ERR_INVALID_PARAMS, "workspace smaller than dllm_token_sample_workspace(M, V, top_k)");
-    const size_t C = tok_chunks(V);
-    if (C > 0x7fffffffu / M) return fail(DLLM_ERR_UNSUPPORTED, "M * ceil(V / 16384) exceeds the grid limit");
-    const unsigned grid = static_cast<unsigned>(M * C), rows = static_cast<unsigned>(M);
-    TokPiece *part = static_cast<TokPiece *>(workspace);
-    const bool masked = top_k > 0 && top_k < V;
-    float *taus = masked ? reinterpret_cast<float *>(part + M * C) : nullptr;
-    const TokTempered xf{r, taus};
-    hipStream_t st = as_stream(stream);
-    const bool f16 = dtype == DLLM_F16;
-    const __half *lh = static_cast<const __half *>(logits);
-    const float *lf = static_cast<const float *>(logits);
-    if (masked) {
-        if (f16)
-            token_select_kernel<<<rows, kSelThreads, 0, st>>>(lh, V, ld, r, static_cast<uint32_t>(top_k), taus);
-        else
-            token_select_kernel<<<rows, kSelThreads, 0, st>>>(lf, V, ld, r, static_cast<uint32_t>(top_k), taus);
-        DLLM_LAUNCH_CHECK();
-    }
-    if (f16)
-        token_chunk_kernel<<<grid, kTokLanes, 0, st>>>(lh, V, ld, C, part, tokens, stats, xf);
-    else
-        token_chunk_kernel<<<grid, kTokLanes, 0, st>>>(lf, V, ld, C, part, tokens, stats, xf);
-    DLLM_LAUNCH_CHECK();
-    if (f16)
-        token_pick_kernel<<<rows, kTokLanes, 0, st>>>(lh, V, ld, C, part, xf, u, seed, offset, tokens, stats);
-    else
-        token_pick_kernel<<<rows, kTokLanes, 0, st>>>(lf, V, ld, C, part, xf, u, seed, offset, tokens, stats);
-    DLLM_LAUNCH_CHECK();
-    return DLLM_OK;
+    if (tok_chunks(V) > 0x7fffffffu / M) return fail(DLLM_ERR_UNSUPPORTED, "M * ceil(V / 16384) exceeds the grid limit");
+    return token_sample_launch<3>(logits, dtype, M, V, ld, r, top_k, false, 0, 0, u, seed, offset, tokens, stats,
+                                  workspace, stream);
+}
+
+int dllm_token_sample_ex(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature, size_t top_k,
+                         float top_p, float min_p, const float *u, uint64_t seed, uint64_t offset, int32_t *tokens,
+                         float *stats, void *workspace, size_t workspace_bytes, dllm_stream_t stream) {
+    if (V == 0) return fail(DLLM_ERR_INVALID_PARAMS, "V == 0: no token to sample from an empty vocabulary");
+    if (ld < V) return fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least V");
+    if (V >= (size_t(1) << 31)) return fail(DLLM_ERR_SHAPE_MISMATCH, "V must be below 2^31 (the token is an int32)");
+    if (dtype != DLLM_F32 && dtype != DLLM_F16) return fail(DLLM_ERR_UNSUPPORTED, "dtype must be DLLM_F32 or DLLM_F16");
+    const float r = 1.0f / temperature;                 // 8j.1: one IEEE division
+    if (!(temperature > 0.0f) || !std::isfinite(temperature) || !std::isfinite(r))
+        return fail(DLLM_ERR_INVALID_PARAMS, "temperature and 1 / temperature must be positive and finite");
+    if (!(top_p > 0.0f) || top_p > 1.0f) return fail(DLLM_ERR_INVALID_PARAMS, "top_p must be in (0, 1]");
+    if (!(min_p >= 0.0f) || min_p > 1.0f) return fail(DLLM_ERR_INVALID_PARAMS, "min_p must be in [0, 1]");
+    if (M == 0) return DLLM_OK;
+    if (!logits || !tokens || !stats || !workspace) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(workspace) % 4)
+        return fail(DLLM_ERR_INVALID_PARAMS, "workspace must be 4-byte aligned");
+    if (workspace_bytes < dllm_token_sample_ex_workspace(M, V, top_k, top_p, min_p))
+        return fail(DLLM_ERR_INVALID_PARAMS,
+                    "workspace smaller than dllm_token_sample_ex_workspace(M, V, top_k, top_p, min_p)");
+    if (tok_chunks(V) > 0x7fffffffu / M) return fail(DLLM_ERR_UNSUPPORTED, "M * ceil(V / 16384) exceeds the grid limit");
+    return token_sample_launch<4>(logits, dtype, M, V, ld, r, top_k, top_p != 1.0f, token::nucleus_pfix(top_p),
+                                  token::nucleus_mfix(min_p), u, seed, offset, tokens, stats, workspace, stream);
 }
 
 }  // extern "C"

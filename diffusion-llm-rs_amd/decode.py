@@ -4,8 +4,8 @@ token (the reference's ``max_by`` fold, ties and NaNs included), stats = {m, Z} 
 the softmax denominator, so that the greedy token's probability is 1 / Z) and, on request, the
 probabilities -- tokens and stats from one read of the logits.  The rule is pinned in
 include/dllm_quant.h (section 8h) and is bit-reproducible on the host.  ``sample_tokens`` is the
-sampling strategy the reference leaves open (section 8j): temperature, top-k and one seeded draw per
-row, pinned and reproducible in the same way.
+sampling strategy the reference leaves open (sections 8j and 8k): temperature, top-k, top-p, min-p and
+one seeded draw per row, pinned and reproducible in the same way.
 """
 from __future__ import annotations
 
@@ -69,12 +69,18 @@ def token_readout(logits: torch.Tensor, probs: bool = False):
 
 
 def sample_tokens(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0, seed: int = 0, offset: int = 0,
-                  u: torch.Tensor = None):
+                  u: torch.Tensor = None, top_p: float = 1.0, min_p: float = 0.0, return_tau: bool = False):
     """dllm_token_sample on logits [M, V] (layouts as ``token_readout``) -> (tokens int32 [M], stats f32
     [M, 3] = {m, Z, p_token}): one token per row drawn from softmax(logits / temperature) restricted to
     the ``top_k`` largest logits (0 = all; ties at the k-th place are all kept).  Row b draws with the
     three uniforms of counter ``offset + b`` of the seeded stream ``seed``, or with ``u[b]`` (f32
-    [M, 3]) when ``u`` is given.  A row with a NaN or +inf, or of -inf, gets token -1 and NaN stats."""
+    [M, 3]) when ``u`` is given.  A row with a NaN or +inf, or of -inf, gets token -1 and NaN stats.
+
+    ``top_p`` < 1 keeps the smallest set of the largest survivors of top-k whose mass reaches ``top_p``
+    (the nucleus), ``min_p`` > 0 keeps what has at least ``min_p`` times the maximum's probability
+    (section 8k; ties at either threshold are all kept).  With either on, or with ``return_tau``, the
+    call is dllm_token_sample_ex; ``return_tau`` makes stats [M, 4] = {m, Z, p_token, tau}, tau being
+    the row's combined threshold on logits / temperature (-inf when no mask is on)."""
     logits, single, M, V, ld = _rows(logits)
     if top_k < 0:
         raise _lib.InvalidParams("top_k must not be negative")
@@ -83,12 +89,23 @@ def sample_tokens(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0
     if u is not None:
         u = u.to(device=dev, dtype=torch.float32).reshape(M, 3).contiguous()
     tokens = torch.empty(M, dtype=torch.int32, device=dev)
-    stats = torch.empty(M, 3, dtype=torch.float32, device=dev)
-    wsb = L.dllm_token_sample_workspace(M, V, top_k)
-    ws = _workspace(dev, wsb)
-    check(L.dllm_token_sample(_ptr(logits), _lib.F16 if logits.dtype == torch.float16 else _lib.F32, M, V, ld,
-                              float(temperature), int(top_k), _ptr(u), seed & (2 ** 64 - 1), offset & (2 ** 64 - 1),
-                              _ptr(tokens), _ptr(stats), _ptr(ws), wsb, _stream()))
+    dtype = _lib.F16 if logits.dtype == torch.float16 else _lib.F32
+    if float(top_p) == 1.0 and float(min_p) == 0.0 and not return_tau:
+        stats = torch.empty(M, 3, dtype=torch.float32, device=dev)
+        wsb = L.dllm_token_sample_workspace(M, V, top_k)
+        ws = _workspace(dev, wsb)
+        check(L.dllm_token_sample(_ptr(logits), dtype, M, V, ld, float(temperature), int(top_k), _ptr(u),
+                                  seed & (2 ** 64 - 1), offset & (2 ** 64 - 1), _ptr(tokens), _ptr(stats), _ptr(ws),
+                                  wsb, _stream()))
+    else:
+        stats = torch.empty(M, 4, dtype=torch.float32, device=dev)
+        wsb = L.dllm_token_sample_ex_workspace(M, V, top_k, float(top_p), float(min_p))
+        ws = _workspace(dev, wsb)
+        check(L.dllm_token_sample_ex(_ptr(logits), dtype, M, V, ld, float(temperature), int(top_k), float(top_p),
+                                     float(min_p), _ptr(u), seed & (2 ** 64 - 1), offset & (2 ** 64 - 1), _ptr(tokens),
+                                     _ptr(stats), _ptr(ws), wsb, _stream()))
+        if not return_tau:
+            stats = stats[:, :3]
     return (tokens[0], stats[0]) if single else (tokens, stats)
 
 
@@ -114,9 +131,9 @@ class TokenHead:
         return tokens, 1.0 / stats[:, 1]
 
     def sample(self, x: torch.Tensor, temperature: float = 1.0, top_k: int = 0, seed: int = 0,
-               offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+               offset: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
         """x [M, K] -> (tokens int32 [M], p_token f32 [M]): ``sample_tokens`` of the layer's logits."""
-        tokens, stats = sample_tokens(self.logits(x), temperature, top_k, seed, offset)
+        tokens, stats = sample_tokens(self.logits(x), temperature, top_k, seed, offset, top_p=top_p, min_p=min_p)
         return tokens, stats[:, 2]
 
     def probabilities(self, x: torch.Tensor) -> torch.Tensor:

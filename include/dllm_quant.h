@@ -780,6 +780,52 @@ int dllm_token_sample(const void *logits, int dtype, size_t M, size_t V, size_t 
                       int32_t *tokens /* [M] */, float *stats /* [M][3] */, void *workspace,
                       size_t workspace_bytes, dllm_stream_t stream);
 
+/* ---- 8k token sampling with top-p (nucleus) and min-p masks -----------------------------------------
+ * dllm_token_sample_ex is dllm_token_sample with two more masks, `top_p` and `min_p` (f32).  Each is a
+ * threshold on the tempered logits y of 8j.1, found with integer sums, so that -- as with top-k -- no
+ * sort order, summation order or selection algorithm can change it.  top_p == 1 turns the nucleus
+ * mask off, min_p == 0 the min-p mask; with both off every output carries dllm_token_sample's bits.
+ * The contract is 8j's: a row's outputs depend on that row's V elements, the four parameters and the
+ * row's three uniforms alone; nothing at or past index V of a row is ever read.
+ * 1. y is 8j.1's.  tau_k is 8j.2's threshold, -inf when top-k is off (top_k == 0 or >= V).  m is the row
+ *    maximum of y as 8h defines it (a zero maximum is +0); top-k never masks it.
+ * 2. Integer weights.  g_i = EXP(RN(y_i - m)), EXP being 8h's; W_i = (u64) trunc(g_i * 2^32), the product
+ *    exact in f32 (a power of two scales it); W_i = 0 for every element with !(y_i >= tau_k).  The
+ *    maximum has W = 2^32, an element of -inf W = 0.  All sums of W are u64 integer sums (V < 2^31 keeps
+ *    them below 2^63), hence order-free.
+ * 3. Top-p.  T = sum_i W_i; pfix = (u64) floor((double) top_p * 2^32), exact in f64, computed once on the
+ *    host; A(t) = sum{W_i : y_i >= t}, -0 equal to +0.  tau_p is the LARGEST value among the row's y_i
+ *    with A(tau_p) * 2^32 >= pfix * T, compared as integers (the products have up to 95 bits).  It
+ *    exists: A(m) >= 2^32 > 0, and A at the smallest survivor of top-k is T.  TIES AT tau_p ARE ALL
+ *    KEPT.  The nucleus is taken over the survivors of top-k (the masks apply in sequence), not over
+ *    the whole row.  top_p == 1 (off): tau_p = -inf.
+ * 4. Min-p.  mfix = (u64) ceil((double) min_p * 2^32), on the host; tau_m = min{y_i : W_i >= mfix}, a
+ *    minimum over a set; EVERYTHING >= tau_m IS KEPT.  Stated as a threshold, the rule does not rest
+ *    on EXP being monotone -- and it is not quite: DESIGN.md records the exhaustive check, 2878 places
+ *    in (-0.25, 0) where EXP steps down by one ulp -- so an element just above tau_m may be kept with a
+ *    weight one unit of 2^-24 short of mfix.  The maximum always qualifies (mfix <= 2^32).
+ *    min_p == 0 (off): tau_m = -inf.
+ * 5. tau = max(tau_k, tau_p, tau_m), -0 equal to +0 and a zero threshold reported as +0.  From here
+ *    8j.3 - 8j.8 apply unchanged with this tau: the same {m, Z}, the same three picks, the same
+ *    uniforms, the same degenerate rows.  A degenerate row (a NaN, m == +inf or -inf) gets token -1 and
+ *    stats = {NaN, NaN, NaN, NaN}.
+ * stats is f32 [M][4] = {m, Z, p_token, tau}; tau == -inf when no mask is on.
+ * Checks, in this order, before anything touches the device: those of 8j up to and including the
+ * temperature's; then !(top_p > 0) or top_p > 1 -> INVALID_PARAMS; !(min_p >= 0) or min_p > 1 ->
+ * INVALID_PARAMS; then M == 0 -> DLLM_OK, nothing written; a NULL logits, tokens, stats or workspace, a
+ * workspace not 4-byte aligned or shorter than dllm_token_sample_ex_workspace(M, V, top_k, top_p, min_p)
+ * -> INVALID_PARAMS.  (M ceil(V / 16384) >= 2^31 -> UNSUPPORTED: the grid.) */
+/* Bytes of device workspace dllm_token_sample_ex needs: the chunk pieces, M * ceil(V / 16384) * 20, and,
+ * when any of the three masks is on, the rows' thresholds, M * 4. */
+size_t dllm_token_sample_ex_workspace(size_t M, size_t V, size_t top_k, float top_p, float min_p);
+/* As dllm_token_sample (asynchronous on `stream`; never synchronises or allocates; graph-capturable
+ * from the first call; no global atomics -- the threshold search sums in LDS with integer atomics,
+ * whose result is order-free; f32 and f16 logits, any ld >= V and any alignment give the same bits). */
+int dllm_token_sample_ex(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature,
+                         size_t top_k, float top_p, float min_p, const float *u /* device [M][3] or NULL */,
+                         uint64_t seed, uint64_t offset, int32_t *tokens /* [M] */, float *stats /* [M][4] */,
+                         void *workspace, size_t workspace_bytes, dllm_stream_t stream);
+
 /* ---- host-slice variants (synchronous; stage through device memory; not graph-capturable) ----
  * The literal shapes of the reference's Rust signatures, for callers holding host slices. */
 /* quantize_tensor(&[f32], u8) -> (Vec<u8>, f32, f32): codes one per byte (quantization.rs:38-68). */
@@ -820,6 +866,11 @@ int dllm_token_readout_host(const void *logits, int dtype, size_t M, size_t V, s
 int dllm_token_sample_host(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature,
                            size_t top_k, const float *u /* [M][3] or NULL */, uint64_t seed, uint64_t offset,
                            int32_t *tokens /* [M] */, float *stats /* [M][3] */);
+/* dllm_token_sample_ex on host slices: the rule of section 8k in plain C++ (a sorted walk with
+ * 128-bit integers), the same bits as the kernels; the same checks and codes. */
+int dllm_token_sample_ex_host(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature,
+                              size_t top_k, float top_p, float min_p, const float *u /* [M][3] or NULL */,
+                              uint64_t seed, uint64_t offset, int32_t *tokens /* [M] */, float *stats /* [M][4] */);
 /* Section 8i on host slices: serial restatements of the reference's loops in plain C++ (no device,
  * no staging, no workspace), the same bits as the kernels; the same checks and codes, minus the
  * workspace's.  The seen-set is host memory of the same size and layout (dllm_dedup_table_bytes,
