@@ -17,7 +17,8 @@ this package is the host-side mirror of the reference's Rust operator surface:
   p_losses objective (per-sample noise MSE in a pinned summation order), the phase-aware
   KVCacheEntry and the denoise loop (last layer fused with p_sample).
 * ``search``       -- exact cosine top-k over the compressed-vector store, scanned on its byte codes
-  (``FusionANN::search`` over ``KVCache``'s records): search_vectors, VectorIndex.
+  (``FusionANN::search`` over ``KVCache``'s records): search_vectors, VectorIndex; and stored rows against stored rows on the int8 matrix cores
+  (``NsRouter::build_graph``): neighbor_rows, VectorIndex.neighbors / build_graph, NavigationGraph.
 * ``decode``       -- the token readout (``DiffusionPrefill``'s predict / ``sample_token`` step): greedy
   tokens, {max, softmax denominator} and probabilities of logits [M, vocab] in a pinned,
   bit-reproducible rule: token_readout, TokenHead; and the sampling step beside it (temperature,
@@ -39,7 +40,7 @@ from .linear import MixedPrecisionStack, QuantLinear
 from .diffusion import (AlphaMode, BetaSchedule, Cumprod, DenoiseLoop, DiffusionConfig, KVCacheEntry, KVCacheStore,
                         add_noise, noise_mse, p_losses, p_losses_coeffs,
                         p_sample, randn)
-from .search import VectorIndex, search_table, search_vectors
+from .search import NavigationGraph, VectorIndex, neighbor_rows, neighbor_table, search_table, search_vectors
 from .decode import TokenHead, sample_tokens, token_readout
 from .dedup import DedupBuffer, dedup_rows, gather_rows, hash_rows, store_vectors
 
@@ -51,6 +52,7 @@ __all__ = [
     "ShapeMismatch", "CalibrationRequired", "HipError", "BetaSchedule", "Cumprod", "AlphaMode", "DiffusionConfig",
     "KVCacheEntry", "KVCacheStore", "DenoiseLoop", "add_noise", "p_sample", "randn", "AdaptiveQuantizer",
     "noise_mse", "p_losses", "p_losses_coeffs", "search_vectors", "search_table", "VectorIndex",
+    "neighbor_table", "neighbor_rows", "NavigationGraph",
     "token_readout", "sample_tokens", "TokenHead", "hash_rows", "dedup_rows", "gather_rows", "DedupBuffer", "store_vectors",
 ]
 

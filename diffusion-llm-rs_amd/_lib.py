@@ -161,6 +161,12 @@ SIGNATURES = {
     "dllm_search_vectors": (INT, [P, S, P, P, S, S, S, P, P, P, S, P]),
     "dllm_search_table_host": (INT, [P, S, S, P, P, P]),
     "dllm_search_vectors_host": (INT, [P, S, P, P, S, S, S, P, P]),
+    "dllm_neighbor_table_bytes": (S, [S]),
+    "dllm_neighbor_table": (INT, [P, S, S, P, P, P, P]),
+    "dllm_neighbor_workspace": (S, [S, S, S]),
+    "dllm_neighbor_rows": (INT, [P, P, S, P, P, S, S, S, FL, C.c_int64, P, P, P, S, P]),
+    "dllm_neighbor_table_host": (INT, [P, S, S, P, P, P]),
+    "dllm_neighbor_rows_host": (INT, [P, P, S, P, P, S, S, S, FL, C.c_int64, P, P]),
     "dllm_token_readout_workspace": (S, [S, S]),
     "dllm_token_readout": (INT, [P, INT, S, S, S, P, P, P, P, S, P]),
     "dllm_token_readout_host": (INT, [P, INT, S, S, S, P, P, P]),

@@ -14,6 +14,7 @@
 
 #include "dedup_rule.hpp"
 #include "dllm_quant.h"
+#include "neighbor_rule.hpp"
 #include "token_exp.hpp"
 #include "token_nucleus_rule.hpp"
 #include "token_sample_rule.hpp"
@@ -532,6 +533,65 @@ int dllm_search_vectors_host(const float *Q, size_t nq, const uint8_t *codes, co
             const uint32_t id = i < top ? ~static_cast<uint32_t>(keys[i]) : 0u;
             idx[j * k + i] = i < top ? static_cast<int32_t>(id) : -1;
             scores[j * k + i] = i < top ? sc[id] : -std::numeric_limits<float>::infinity();
+        }
+    }
+    return DLLM_OK;
+}
+
+// ---- section 8l on host slices: the rule of neighbor_rule.hpp row by row, ranked with a sort ----
+
+int dllm_neighbor_table_host(const uint8_t *codes, size_t rows, size_t dim, const float *scales, const float *zps,
+                             void *table) {
+    if (int rc = search_shape_ok(rows, dim)) return rc;
+    if (rows == 0) return DLLM_OK;
+    if (!codes || !scales || !zps || !table) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(table) % 8) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "table must be 8-byte aligned");
+    dllm::neighbor::Entry *out = static_cast<dllm::neighbor::Entry *>(table);
+    for (size_t r = 0; r < rows; ++r) {
+        uint32_t c1 = 0, c2 = 0;
+        for (size_t d = 0; d < dim; ++d) {
+            const uint32_t c = codes[r * dim + d];
+            c1 += c;
+            c2 += c * c;
+        }
+        out[r] = dllm::neighbor::make_entry(scales[r], zps[r], c1, c2, static_cast<uint32_t>(dim));
+    }
+    return DLLM_OK;
+}
+
+int dllm_neighbor_rows_host(const uint8_t *qcodes, const void *qtable, size_t nq, const uint8_t *codes,
+                            const void *table, size_t rows, size_t dim, size_t k, float threshold, int64_t self_base,
+                            int32_t *idx, float *scores) {
+    namespace nb = dllm::neighbor;
+    if (k == 0 || k > nb::kMaxK) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "k must be between 1 and 256");
+    if (int rc = search_shape_ok(rows, dim)) return rc;
+    if (threshold != threshold) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "threshold must not be NaN");
+    if (self_base < -1) return dllm::fail(DLLM_ERR_INVALID_PARAMS, "self_base must be -1 or a row of the store");
+    if (self_base >= 0 && (static_cast<uint64_t>(self_base) > rows || nq > rows - static_cast<uint64_t>(self_base)))
+        return dllm::fail(DLLM_ERR_INVALID_PARAMS, "self_base + nq exceeds rows");
+    if (nq == 0) return DLLM_OK;
+    if (!qcodes || !qtable || !idx || !scores || (rows && (!codes || !table)))
+        return dllm::fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(qtable) % 8 || reinterpret_cast<uintptr_t>(table) % 8)
+        return dllm::fail(DLLM_ERR_INVALID_PARAMS, "qtable and table must be 8-byte aligned");
+    const nb::Entry *qt = static_cast<const nb::Entry *>(qtable), *tt = static_cast<const nb::Entry *>(table);
+    std::vector<float> sc(rows);
+    std::vector<uint64_t> keys;
+    keys.reserve(rows);
+    for (size_t j = 0; j < nq; ++j) {
+        keys.clear();
+        for (size_t t = 0; t < rows; ++t) {
+            uint32_t D = 0;                                 // < 2^32: dim <= 65535
+            for (size_t d = 0; d < dim; ++d) D += static_cast<uint32_t>(qcodes[j * dim + d]) * codes[t * dim + d];
+            sc[t] = nb::score(qt[j].a, qt[j].b, qt[j].c1, tt[t].a, tt[t].b, tt[t].c1, D, static_cast<uint32_t>(dim));
+            if (!nb::dropped(sc[t], threshold, self_base, j, t)) keys.push_back(search_key(sc[t], static_cast<uint32_t>(t)));
+        }
+        std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
+        for (size_t i = 0; i < k; ++i) {
+            const bool has = i < keys.size();
+            const uint32_t id = has ? ~static_cast<uint32_t>(keys[i]) : 0u;
+            idx[j * k + i] = has ? static_cast<int32_t>(id) : -1;
+            scores[j * k + i] = has ? sc[id] : -std::numeric_limits<float>::infinity();
         }
     }
     return DLLM_OK;

@@ -18,6 +18,7 @@
 //
 // Reference: diffusion_prefill/src/fusion_ann.rs:109-136 (cosine, sort descending, take k).
 #include "common.hpp"
+#include "search_select.hpp"
 
 #include <cmath>
 
@@ -298,8 +299,9 @@ __device__ __forceinline__ void select_stage(uint64_t *s, unsigned len, unsigned
 // neighbouring runs by the elementwise larger of the two (a descending run followed by an ascending
 // one is bitonic, so those are its K largest, again bitonic), halving the data, and re-sorts the runs
 // with the log2 K merge stages.  Keys are unique, so the result is the sort's first k whatever the
-// route.
-template <bool FROM_SCORES>
+// route.  DROP (with FROM_SCORES): a NaN score is no row at all (key 0), the sentinel of a producer
+// whose rule never yields a NaN (neighbors.hip's dropped pairs).
+template <bool FROM_SCORES, bool DROP = false>
 __global__ void __launch_bounds__(kSelThreads) search_select_kernel(const float *__restrict__ scores,
                                                                     const uint64_t *__restrict__ keys_in, size_t n,
                                                                     size_t nsl, size_t rows, unsigned k,
@@ -319,7 +321,14 @@ __global__ void __launch_bounds__(kSelThreads) search_select_kernel(const float 
     for (unsigned i = tid; i < fill; i += kSelThreads) {
         const size_t e = base + i;
         uint64_t key = 0;
-        if (i < cnt) key = FROM_SCORES ? search_key(scores[j * rows + e], static_cast<uint32_t>(e)) : keys_in[j * n + e];
+        if (i < cnt) {
+            if (FROM_SCORES) {
+                const float sc = scores[j * rows + e];
+                key = (DROP && sc != sc) ? 0 : search_key(sc, static_cast<uint32_t>(e));
+            } else {
+                key = keys_in[j * n + e];
+            }
+        }
         s[i] = key;
     }
     __syncthreads();
@@ -405,6 +414,49 @@ int check_store_shape(size_t rows, size_t dim) {
 }
 
 }  // namespace
+
+SelectPlan select_plan(size_t nq, size_t rows, size_t k) {
+    const SearchPlan p = search_plan(nq, rows, k);
+    SelectPlan s;
+    s.keys_a = p.keys_b - p.keys_a;
+    s.keys_b = p.total - p.keys_b;
+    return s;
+}
+
+bool select_grid_ok(size_t nq, size_t rows) { return rows == 0 || nq <= 0x7fffffffu / slices_of(rows); }
+
+int select_topk(const float *sc, size_t nq, size_t rows, size_t k, uint64_t *keys_a, uint64_t *keys_b, int32_t *idx,
+                float *scores, bool drop_nan, hipStream_t st) {
+    uint64_t *keys[2] = {keys_a, keys_b};
+    size_t n = rows;
+    int pass = 0;
+    for (;; ++pass) {
+        const size_t nsl = slices_of(n);
+        const int final = nsl == 1;
+        const unsigned grid = static_cast<unsigned>(nq * nsl);
+        uint64_t *dst = keys[pass & 1];
+        if (pass == 0 && drop_nan)
+            search_select_kernel<true, true><<<grid, kSelThreads, 0, st>>>(sc, nullptr, n, nsl, rows, static_cast<unsigned>(k),
+                                                                           dst, idx, scores, final);
+        else if (pass == 0)
+            search_select_kernel<true><<<grid, kSelThreads, 0, st>>>(sc, nullptr, n, nsl, rows, static_cast<unsigned>(k),
+                                                                     dst, idx, scores, final);
+        else
+            search_select_kernel<false><<<grid, kSelThreads, 0, st>>>(sc, keys[(pass - 1) & 1], n, nsl, rows,
+                                                                      static_cast<unsigned>(k), dst, idx, scores, final);
+        DLLM_LAUNCH_CHECK();
+        if (final) break;
+        n = nsl * k;
+    }
+    return DLLM_OK;
+}
+
+int select_fill_empty(size_t n, int32_t *idx, float *scores, hipStream_t st) {
+    search_fill_empty_kernel<<<grid_for(n, 256, 0x7fffffffu), 256, 0, st>>>(n, idx, scores);
+    DLLM_LAUNCH_CHECK();
+    return DLLM_OK;
+}
+
 }  // namespace dllm
 
 using namespace dllm;
@@ -467,23 +519,7 @@ int dllm_search_vectors(const float *Q, size_t nq, const uint8_t *codes, const f
     if ((nq - j0) & 1) launch_scan<1>(aligned, dim3(gx, 1), st, Q, codes, table, qstat, rows, dim, j0, sc);
     DLLM_LAUNCH_CHECK();
 
-    size_t n = rows;
-    int pass = 0;
-    for (;; ++pass) {
-        const size_t nsl = slices_of(n);
-        const int final = nsl == 1;
-        const unsigned grid = static_cast<unsigned>(nq * nsl);
-        uint64_t *dst = keys[pass & 1];
-        if (pass == 0)
-            search_select_kernel<true><<<grid, kSelThreads, 0, st>>>(sc, nullptr, n, nsl, rows, static_cast<unsigned>(k),
-                                                                     dst, idx, scores, final);
-        else
-            search_select_kernel<false><<<grid, kSelThreads, 0, st>>>(sc, keys[(pass - 1) & 1], n, nsl, rows,
-                                                                      static_cast<unsigned>(k), dst, idx, scores, final);
-        DLLM_LAUNCH_CHECK();
-        if (final) break;
-        n = nsl * k;
-    }
+    if (int rc = select_topk(sc, nq, rows, k, keys[0], keys[1], idx, scores, false, st)) return rc;
     return DLLM_OK;
 }
 

@@ -3,10 +3,15 @@
 records ``KVCache`` keeps, prefill_kv.rs:69-140).  The scan reads the byte codes that
 ``compress_vectors`` wrote and folds the dequantization into the score; the rule is pinned in
 include/dllm_quant.h (section 8g) and is bit-reproducible on the host.
+
+Stored rows against stored rows (``neighbor_rows``, ``VectorIndex.neighbors`` / ``build_graph``) is the
+navigation graph of ``ns-router-rs`` (``NsRouter::build_graph``, lib.rs:99-133): both operands are byte
+codes, the dot product an exact integer off the int8 matrix cores; the rule is section 8l.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -16,6 +21,7 @@ from .kvquant import compress_vectors, decompress_vectors
 from .quantization import _dev, _ptr, _stream
 
 MAX_K = 256
+GRAPH_WORKSPACE_BUDGET = 256 << 20      # bytes of workspace build_graph's default block stays under
 
 
 def search_table(codes: torch.Tensor, scales: torch.Tensor, zps: torch.Tensor) -> torch.Tensor:
@@ -61,6 +67,94 @@ def search_vectors(queries: torch.Tensor, codes: torch.Tensor, scales: torch.Ten
     return (idx[0], scores[0]) if single else (idx, scores)
 
 
+def neighbor_table(codes: torch.Tensor, scales: torch.Tensor, zps: torch.Tensor) -> torch.Tensor:
+    """dllm_neighbor_table: the opaque per-row pair table (uint8 [rows, dllm_neighbor_table_bytes(1)]);
+    a row's entry depends on that row alone, so ``table[a:b]`` is the table of rows a..b."""
+    q = _dev(codes, torch.uint8)
+    rows, dim = q.shape
+    L = _lib.load()
+    per = L.dllm_neighbor_table_bytes(1)
+    table = torch.empty(rows, per, dtype=torch.uint8, device=q.device)
+    check(L.dllm_neighbor_table(_ptr(q), rows, dim, _ptr(_dev(scales, torch.float32)), _ptr(_dev(zps, torch.float32)),
+                                _ptr(table), _stream()))
+    return table
+
+
+def _as_table(table: torch.Tensor, rows: int) -> torch.Tensor:
+    table = _dev(table, torch.uint8)
+    if table.numel() != _lib.load().dllm_neighbor_table_bytes(rows):
+        raise _lib.ShapeMismatch("table must be the neighbor_table of the same rows")
+    return table
+
+
+def neighbor_rows(qcodes: torch.Tensor, qscales: Optional[torch.Tensor], qzps: Optional[torch.Tensor],
+                  codes: torch.Tensor, scales: Optional[torch.Tensor], zps: Optional[torch.Tensor], k: int,
+                  threshold: float = -math.inf, self_base: int = -1, qtable: Optional[torch.Tensor] = None,
+                  table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k rows of the store nearest by cosine to each query row, the queries being compressed rows
+    themselves (a block of the same store, or rows of another store of the same dim) -> (idx int32
+    [nq, k], scores f32 [nq, k]) in rank order.  A pair is left out when it is the query's own row
+    (``self_base`` >= 0: query j is row self_base + j of the store) or its score is below ``threshold``;
+    such places and those past the end are index -1, score -inf.  ``qtable`` / ``table``: prebuilt
+    ``neighbor_table`` of the queries / the store (then the scales and zero points may be None)."""
+    qc, c = _dev(qcodes, torch.uint8), _dev(codes, torch.uint8)
+    if qc.dim() != 2 or c.dim() != 2 or qc.shape[1] != c.shape[1]:
+        raise _lib.ShapeMismatch(f"query rows have {tuple(qc.shape)[1:]} codes, the store's rows {tuple(c.shape)[1:]}")
+    (nq, dim), rows, k = qc.shape, c.shape[0], int(k)
+    if not 1 <= k <= MAX_K:
+        raise _lib.InvalidParams("k must be between 1 and 256")
+    qtable = neighbor_table(qc, qscales, qzps) if qtable is None else _as_table(qtable, nq)
+    table = neighbor_table(c, scales, zps) if table is None else _as_table(table, rows)
+    L = _lib.load()
+    idx = torch.empty(nq, k, dtype=torch.int32, device=c.device)
+    out = torch.empty(nq, k, dtype=torch.float32, device=c.device)
+    wsb = L.dllm_neighbor_workspace(nq, rows, k)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=c.device)
+    check(L.dllm_neighbor_rows(_ptr(qc), _ptr(qtable), nq, _ptr(c), _ptr(table), rows, dim, k, float(threshold),
+                               int(self_base), _ptr(idx), _ptr(out), _ptr(ws), wsb, _stream()))
+    return idx, out
+
+
+class NavigationGraph:
+    """``NsRouter::build_graph``'s ``DiGraph<String, f32>`` (ns-router-rs/src/lib.rs:99-133): one node per
+    stored vector, up to k edges from each node to its nearest other nodes, weight = cosine.
+    ``ids``: row -> id; ``idx`` / ``scores``: device tensors [n, k], -1 / -inf where a node has fewer edges."""
+
+    def __init__(self, ids: Sequence[int], idx: torch.Tensor, scores: torch.Tensor):
+        self.ids = [int(i) for i in ids]
+        self.idx, self.scores = idx, scores
+        self._row = {i: r for r, i in enumerate(self.ids)}
+        self._host = None
+
+    def __len__(self) -> int:
+        return len(self.ids)
+
+    def _lists(self):
+        if self._host is None:
+            self._host = (self.idx.cpu().tolist(), self.scores.cpu().tolist())
+        return self._host
+
+    def neighbors(self, id: int) -> List[Tuple[int, float]]:
+        """One node's edges, [(id, cosine)] in rank order; [] for an id that is no node."""
+        r = self._row.get(int(id), -1)
+        if r < 0:
+            return []
+        idx, sc = self._lists()
+        return [(self.ids[t], s) for t, s in zip(idx[r], sc[r]) if t >= 0]
+
+    def edges(self) -> List[Tuple[int, int, float]]:
+        """[(id_a, id_b, weight)], node by node in row order, each node's edges in rank order."""
+        idx, sc = self._lists()
+        return [(self.ids[r], self.ids[t], s) for r in range(len(self.ids)) for t, s in zip(idx[r], sc[r]) if t >= 0]
+
+
+def graph_block(n: int, k: int, budget: int = GRAPH_WORKSPACE_BUDGET) -> int:
+    """Query rows per call that keep dllm_neighbor_workspace(block, n, k) under ``budget`` bytes: the
+    score matrix is 4 n bytes per query row and the select keys at most 8 k ceil(n / 2048) (1 + 1 / 8)."""
+    per_row = 4 * n + 9 * k * (-(-n // 2048)) + 16
+    return max(1, min(n, budget // per_row))
+
+
 class VectorIndex:
     """``KVCache`` (prefill_kv.rs:69-140) with ``FusionANN::search`` over it: vectors are compressed
     on insert (``compress_vector``, :104-121), kept as rows of one device store and searched on their
@@ -75,6 +169,7 @@ class VectorIndex:
         self._slot: Dict[int, int] = {}     # id -> row of the store
         self._ids: List[int] = []           # row -> id
         self._codes = self._scales = self._zps = self._table = None   # device tensors, rows = capacity
+        self._pairs = None                  # the neighbor_table of rows [0, len), built on demand
 
     def __len__(self) -> int:
         return len(self._ids)
@@ -131,6 +226,7 @@ class VectorIndex:
         codes, scales, zps = compress_vectors(x, self.bits)
         table = search_table(codes, scales, zps)
         rows, keep = self._assign(ids)
+        self._pairs = None
         self._reserve(len(self._ids), x.device)
         at = torch.tensor(rows, dtype=torch.long, device=x.device)
         if len(keep) != len(ids):
@@ -165,3 +261,52 @@ class VectorIndex:
 
     def search(self, query: torch.Tensor, k: int) -> List[Tuple[int, float]]:
         return self.search_batch(_dev(query, torch.float32).reshape(1, -1), k)[0]
+
+    # ---- rows against rows (ns-router-rs build_graph) ----------------------------------------------
+    def _pair_table(self) -> torch.Tensor:
+        """The pair table of the stored rows: built on the first use after an insert, then kept."""
+        if self._pairs is None:
+            n = len(self._ids)
+            self._pairs = neighbor_table(self._codes[:n], self._scales[:n], self._zps[:n])
+        return self._pairs
+
+    def neighbors(self, ids: Sequence[int], k: int, threshold: float = -math.inf) -> List[List[Tuple[int, float]]]:
+        """Per id the stored vectors nearest to that stored vector, [(id, cosine)] in rank order, the
+        vector itself excluded and scores below ``threshold`` left out; [] for a missing id."""
+        if not 1 <= int(k) <= MAX_K:
+            raise _lib.InvalidParams("k must be between 1 and 256")
+        rows = self._lookup(ids)
+        found = [p for p, r in enumerate(rows) if r >= 0]
+        out: List[List[Tuple[int, float]]] = [[] for _ in rows]
+        if not found:
+            return out
+        n = len(self._ids)
+        table = self._pair_table()
+        for p in found:                     # one call per id: its own row is a different self_base each
+            r = rows[p]
+            idx, sc = neighbor_rows(self._codes[r:r + 1], None, None, self._codes[:n], None, None, k, threshold,
+                                    self_base=r, qtable=table[r:r + 1], table=table)
+            out[p] = [(self._ids[t], s) for t, s in zip(idx[0].cpu().tolist(), sc[0].cpu().tolist()) if t >= 0]
+        return out
+
+    def build_graph(self, k: int, threshold: float = 0.8, block: Optional[int] = None) -> NavigationGraph:
+        """``NsRouter::build_graph``: every stored vector against every other, up to k edges per node with
+        cosine >= ``threshold`` (``SystemConfig::similarity_threshold``).  The store is walked in blocks of
+        ``block`` query rows (default: ``graph_block``, which keeps a call's workspace under
+        GRAPH_WORKSPACE_BUDGET); a ragged last block is the normal case."""
+        if not 1 <= int(k) <= MAX_K:
+            raise _lib.InvalidParams("k must be between 1 and 256")
+        n, k = len(self._ids), int(k)
+        if block is not None and int(block) < 1:
+            raise _lib.InvalidParams("block must be at least 1")
+        dev = self._codes.device if self._codes is not None else torch.device("cuda")
+        idx = torch.empty(n, k, dtype=torch.int32, device=dev)
+        sc = torch.empty(n, k, dtype=torch.float32, device=dev)
+        if n:
+            step = graph_block(n, k) if block is None else int(block)
+            table = self._pair_table()
+            for r0 in range(0, n, step):
+                r1 = min(n, r0 + step)
+                idx[r0:r1], sc[r0:r1] = neighbor_rows(self._codes[r0:r1], None, None, self._codes[:n], None, None, k,
+                                                      threshold, self_base=r0, qtable=table[r0:r1], table=table)
+        return NavigationGraph(self._ids, idx, sc)

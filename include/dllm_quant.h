@@ -826,6 +826,78 @@ int dllm_token_sample_ex(const void *logits, int dtype, size_t M, size_t V, size
                          uint64_t seed, uint64_t offset, int32_t *tokens /* [M] */, float *stats /* [M][4] */,
                          void *workspace, size_t workspace_bytes, dllm_stream_t stream);
 
+/* ---- 8l navigation graph: exact cosine k-NN between stored rows, on the int8 matrix cores ----------
+ * NsRouter::build_graph (ns-router-rs/src/lib.rs:99-128) adds one node per vector and calls
+ * build_edges, whose body reads "Implementation would calculate similarities and create edges"
+ * (:130-133; SystemConfig::similarity_threshold 0.8, :68-81; diffusion_prefill/src/router.rs:103-107
+ * add_similarity_edges has the same hole).  This section scores stored rows against stored rows: both
+ * sides are what dllm_compress_vectors emits (codes u8 [rows][dim], scales and zps f32 [rows]), the
+ * queries a block of the same store or rows of another store of the same dim.  A row is the algebraic
+ * vector v_d = s c_d + z with s, z widened exactly to f64; nothing is dequantized, and
+ *   v_r . v_t = s_r s_t D + s_r z_t C1_r + z_r s_t C1_t + z_r z_t dim,   D = sum_d c_r[d] c_t[d].
+ *
+ * The rule.
+ *   Pair table (dllm_neighbor_table; once per store).  C1 = sum c, C2 = sum c^2: exact u32 (dim <=
+ *   65535).  In f64, separate IEEE multiplies and adds, exactly as 8g:
+ *   nb2 = ((s s) C2 + ((2 s) z) C1) + (z z) dim;  w = 1.0 / sqrt(nb2) (correctly rounded f64 sqrt and
+ *   divide) if s, z and nb2 are finite and nb2 > 0, else w = 0;  a = s w, b = z w (f64 multiplies; with
+ *   w = 0, a = b = +0).  The table holds (a, b, C1) per row: dllm_neighbor_table_bytes(rows) bytes,
+ *   8-byte aligned, opaque to callers; the entry of a row depends on that row alone, so a slice of a
+ *   table is the table of the slice.
+ *   Pair (query row r, store row t).  D is an exact integer, D <= 65535 * 255^2 < 2^32.
+ *   score = (float)( ((a_r a_t) D + ((a_r b_t) C1_r + (b_r a_t) C1_t)) + (b_r b_t) dim ):  every
+ *   operation a separately rounded f64 multiply or add, no fma; D, C1 and dim converted to f64
+ *   exactly; the final cast rounds to nearest even.
+ * Properties.  The score depends on the two rows alone: not on nq, rows, k, the block of queries, the
+ * grid, the tile or k order of the matrix instruction, or the device (D is an integer, so no order of
+ * summation exists to pin).  score(r, t) and score(t, r) have the same bits: f64 + and x commute, and
+ * the two cross terms are added to each other before anything else.  A zero-norm row or a row with a
+ * non-finite s or z has a = b = +0 and scores +0 against everything (as 8g and fusion_ann.rs:131-135).
+ * A score is never NaN: |a| |c|_2 and |b| sqrt(dim) are at most kappa (below), finite, so every product
+ * and sum above is finite.
+ * Error bound.  For finite rows with nb2 > 0, against the exact cosine of the two algebraic vectors,
+ * with kappa_r = (|s| |c|_2 + |z| sqrt(dim)) / |v|_2 >= 1 and u = 2^-53, to first order
+ *   |score - cos| <= 2^-25 + 12 u kappa_r kappa_t + 2^-51 (kappa_r^3 + kappa_t^3) / 2
+ * (2^-25: the final f32 rounding of a value of magnitude <= 1.  Each of the four terms is at most
+ * kappa_r kappa_t in magnitude by Cauchy-Schwarz -- a_r a_t D <= (|a_r| |c_r|)(|a_t| |c_t|), and so on
+ * -- and so is every partial sum; a term carries the roundings of a, a', their product and the
+ * product with the integer, 4 u, plus the relative error of w_r w_t; three additions add 3 u; in all
+ * fewer than 12 u kappa_r kappa_t apart from w.  w_r = 1 / sqrt(nb2_r) inherits half the relative
+ * error of nb2_r, which is 8g's 2^-51 kappa_r^2 from the cancellation inside nb2, times the kappa_r of
+ * the term it scales: 2^-52 kappa_r^3, and the same for t.)  For the stores of dllm_compress_vectors
+ * kappa is a few units and the bound is 2^-25 (1 + 10^-6).
+ * Ranking, exclusion, threshold.  Rank by 8g's key: score descending, row index ascending, -0 equal
+ * to +0; keys are unique.  A pair is dropped if it is the query's own row (self_base >= 0: query j is
+ * row self_base + j of the store) or if !(score >= threshold).  Dropped pairs and the places past the
+ * end come out as index -1, score -inf.  threshold == -inf drops nothing; a score equal to the
+ * threshold is kept; threshold == +inf drops everything. */
+/* Bytes of the pair table of `rows` rows. */
+size_t dllm_neighbor_table_bytes(size_t rows);
+/* table (device, dllm_neighbor_table_bytes(rows) bytes, 8-byte aligned) = the pair table; one read of
+ * the codes.  dim == 0 or > 65535 -> INVALID_PARAMS; rows >= 2^31 -> SHAPE_MISMATCH; rows == 0 ->
+ * DLLM_OK; a NULL pointer or a misaligned table -> INVALID_PARAMS.  Asynchronous on `stream`. */
+int dllm_neighbor_table(const uint8_t *codes, size_t rows, size_t dim, const float *scales, const float *zps,
+                        void *table, dllm_stream_t stream);
+/* Bytes of device workspace dllm_neighbor_rows needs: the score matrix f32 [nq][rows] and the select
+ * passes' candidate keys. */
+size_t dllm_neighbor_workspace(size_t nq, size_t rows, size_t k);
+/* idx (device i32 [nq][k]) and scores (device f32 [nq][k]): for each of the nq query rows (qcodes u8
+ * [nq][dim] with its pair table qtable) the k best rows of the store (codes, table) in rank order.
+ * Any dim in 1..65535 and any alignment of codes and qcodes give the same bits; nothing at or past
+ * codes + rows dim (qcodes + nq dim) is read.  Checked in this order, before anything touches the
+ * device: k == 0 or k > 256 -> INVALID_PARAMS; dim == 0 or > 65535 -> INVALID_PARAMS; rows >= 2^31 ->
+ * SHAPE_MISMATCH; a NaN threshold -> INVALID_PARAMS; self_base < -1, or self_base >= 0 with
+ * self_base + nq > rows -> INVALID_PARAMS; nq == 0 -> DLLM_OK, nothing written; a NULL qcodes, qtable,
+ * idx or scores (codes or table with rows > 0), or a qtable or table that is not 8-byte aligned ->
+ * INVALID_PARAMS; rows == 0 -> DLLM_OK, the outputs filled with -1 / -inf; workspace NULL, not 16-byte
+ * aligned or shorter than dllm_neighbor_workspace(nq, rows, k) -> INVALID_PARAMS.  (nq ceil(rows /
+ * 2048) >= 2^31 -> SHAPE_MISMATCH: the grid.)  Asynchronous on `stream`; never synchronises or
+ * allocates (graph-capturable from the first call); no atomics. */
+int dllm_neighbor_rows(const uint8_t *qcodes, const void *qtable, size_t nq, const uint8_t *codes, const void *table,
+                       size_t rows, size_t dim, size_t k, float threshold, int64_t self_base,
+                       int32_t *idx /* [nq][k] */, float *scores /* [nq][k] */, void *workspace,
+                       size_t workspace_bytes, dllm_stream_t stream);
+
 /* ---- host-slice variants (synchronous; stage through device memory; not graph-capturable) ----
  * The literal shapes of the reference's Rust signatures, for callers holding host slices. */
 /* quantize_tensor(&[f32], u8) -> (Vec<u8>, f32, f32): codes one per byte (quantization.rs:38-68). */
@@ -857,6 +929,14 @@ int dllm_search_table_host(const uint8_t *codes, size_t rows, size_t dim, const 
                            float *table /* [rows][2] */);
 int dllm_search_vectors_host(const float *Q, size_t nq, const uint8_t *codes, const float *table, size_t rows,
                              size_t dim, size_t k, int32_t *idx /* [nq][k] */, float *scores /* [nq][k] */);
+/* dllm_neighbor_table / dllm_neighbor_rows on host slices: the rule of section 8l in plain C++ (no
+ * device, no staging, no workspace; ranked with a sort on the key), the same bits as the kernels; the
+ * same checks and codes, minus the workspace's.  A table copied between host and device stays valid. */
+int dllm_neighbor_table_host(const uint8_t *codes, size_t rows, size_t dim, const float *scales, const float *zps,
+                             void *table);
+int dllm_neighbor_rows_host(const uint8_t *qcodes, const void *qtable, size_t nq, const uint8_t *codes,
+                            const void *table, size_t rows, size_t dim, size_t k, float threshold, int64_t self_base,
+                            int32_t *idx /* [nq][k] */, float *scores /* [nq][k] */);
 /* dllm_token_readout on host slices: the rule of section 8h in plain C++ (no device, no staging, no
  * workspace), the same bits as the kernels; the same checks and codes. */
 int dllm_token_readout_host(const void *logits, int dtype, size_t M, size_t V, size_t ld, int32_t *tokens,

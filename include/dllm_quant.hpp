@@ -377,6 +377,30 @@ inline std::vector<std::pair<std::string, float>> search(const std::vector<Compr
     for (size_t i = 0; i < k && idx[i] >= 0; ++i) out.emplace_back(store[idx[i]].id, scores[i]);
     return out;
 }
+// NsRouter::build_graph's edges (ns-router-rs/src/lib.rs:99-133) over stored CompressedVectors of one
+// length: for every stored vector the ids and cosines of its k nearest other vectors with cosine >=
+// threshold, by dllm_quant.h 8l's rule on the byte codes (host form).  out[r] are node r's edges.
+inline std::vector<std::vector<std::pair<std::string, float>>> build_edges(const std::vector<CompressedVector> &store,
+                                                                           size_t k, float threshold = 0.8f) {
+    const size_t rows = store.size(), dim = rows ? store[0].data.size() : 1;
+    std::vector<uint8_t> codes(rows * dim);
+    std::vector<float> scales(rows), zps(rows), scores(rows * k);
+    std::vector<int32_t> idx(rows * k);
+    std::vector<uint64_t> table((dllm_neighbor_table_bytes(rows) + 7) / 8);       // 8-byte aligned
+    for (size_t r = 0; r < rows; ++r) {
+        if (store[r].data.size() != dim) throw QuantizationError(DLLM_ERR_SHAPE_MISMATCH, "stored vectors differ in length");
+        std::copy(store[r].data.begin(), store[r].data.end(), codes.begin() + r * dim);
+        scales[r] = store[r].quant_scale;
+        zps[r] = store[r].quant_zero_point;
+    }
+    detail::check(dllm_neighbor_table_host(codes.data(), rows, dim, scales.data(), zps.data(), table.data()));
+    detail::check(dllm_neighbor_rows_host(codes.data(), table.data(), rows, codes.data(), table.data(), rows, dim, k,
+                                          threshold, 0, idx.data(), scores.data()));
+    std::vector<std::vector<std::pair<std::string, float>>> out(rows);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t i = 0; i < k && idx[r * k + i] >= 0; ++i) out[r].emplace_back(store[idx[r * k + i]].id, scores[r * k + i]);
+    return out;
+}
 }  // namespace diffusion_prefill
 
 namespace io_dedup {
