@@ -23,6 +23,14 @@ void launch_horner_t(const HornerGemmArgs &a, int y_f32, hipStream_t st, int gro
 }
 
 int launch_horner_lab(const HornerGemmArgs &a, int y_f32, hipStream_t st) {
+    if (a.lab == 49 || a.lab == 50) {   // the skewed 4-slot ring (47) with the lane swaps of make_a dropped (49:
+                                        // results wrong, timing only) / with the A-fragment words read in
+                                        // fragment order (50, bit-identical: the product)
+        if (a.lab == 49) launch_horner16_t<kH16Ring4Skew | 32768>(a, y_f32, st);
+        else launch_horner16_t<kH16Ring4SkewFrag>(a, y_f32, st);
+        DLLM_LAUNCH_CHECK();
+        return DLLM_OK;
+    }
     if (a.lab >= 46 && a.lab <= 48) {   // lab A/B (bit-identical): the 4-slot ring in lockstep (46) / with the
                                         // skew (47), the 3-slot two-barrier ring (48)
         if (a.lab == 46) launch_horner16_t<kH16Ring4>(a, y_f32, st);

@@ -427,6 +427,17 @@ wq_horner_kg2_kernel(const __half *__restrict__ X, int M, int K, const uint32_t 
 // lane's row in the same order, one ds_read_b128 from the swizzled X tile.  D: lane holds columns
 // 16 cb + 4 (lane >> 4) + i of token 16 tb + (lane & 15), so the Horner ratios, the last group's
 // scales and the bias are one float4 per column block.
+// Fragment-order reads (MODE bit 14, the product schedule at int4): the swap only regroups words that
+// the wave has just read from its own LDS ring, the same way every k-step, so the lane reads the
+// words the swap would have left it instead.  Lane L (row rho = L >> 4, i = L & 15) takes word
+// 2h + (rho & 1) of source lane i + 32 (rho >> 1) for column block 0 and the same word of the lane
+// 16 above (256 B further in the wave's 1-KiB piece) for column block 1: dwords 0, 2, 64 and 66 from
+// one per-lane base, two ds_read2_b32 per k-step, and no v_permlane16_swap.  The lane then
+// dequantizes column i for block 0 and column 16 + i for block 1, so it keeps both columns'
+// zero-point constants (two ExactConsts per group).  Each MFMA lane receives the value the swap gave
+// it: the same bits.  The reads are 2-way bank-conflicted (dword 4 i + (rho & 1) + 128 (rho >> 1):
+// 32 banks of 64, the lane rows 2 apart alias), 8 LDS cycles each against the 32 ds_read_b128 of the
+// k-step's B fragments.
 typedef float fx4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
@@ -505,6 +516,13 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
     static_assert(BITS == 4 || (BITS == 2 && TB == 16), "int4, or int2 on 256-token tiles");
     using L = H16<TB>;
     constexpr bool RING4 = (MODE & 8192) != 0;
+    // MODE bit 14: the A-fragment words read from the wave's ring in fragment order, no lane swaps
+    // (int4; the int2 instance of the same MODE keeps the swap).  Bit 15 (lab ablation, results wrong,
+    // timing only): the parent's reads with the swaps dropped.
+    constexpr bool FRAG = (MODE & 16384) != 0 && BITS == 4;
+    constexpr bool NOSWAP = (MODE & 32768) != 0;
+    static_assert((MODE & (16384 | 32768)) == 0 || RING4, "fragment-order reads: the 4-slot ring's private word rings");
+    static_assert((MODE & 16384) == 0 || (MODE & 32768) == 0, "bit 15 ablates the swap that bit 14 has not got");
     static_assert(!RING4 || (TB == 16 && (MODE & (256 | 1024)) == (256 | 1024) && (MODE & (2048 | 64 | 8)) == 0),
                   "the 4-slot ring: 256-token tiles, spread pieces, half 1's A fragments after substep 1");
     // RING4: a slot holds X and the group data only (34 KiB); the weight words live in a wave-private
@@ -615,15 +633,21 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
                                                       (sj_tb0(j) + i) * 16 * kBK * 2);
     };
 
-    ExactConsts ec;
+    ExactConsts ec, ec1;   // ec1 (FRAG): column 16 + i, column block 1's
     uint32_t w[BITS];
     float4 r4[2];
     half8_t bA[8], bB[8], a00, a01, a10, a11;
+    // FRAG: the lane's base within the wave's 1-KiB piece (source lane i + 32 (rho >> 1), word rho & 1)
+    const uint32_t wfrag = static_cast<uint32_t>((row16 + 32 * (rq >> 1)) * 16 + (rq & 1) * 4);
     // par: the k-step's parity (BITS = 2: which half of the pair's piece)
     auto load_w = [&](const uint8_t *sb, int kk, int par) __attribute__((always_inline)) {
         if constexpr (RING4) {   // the wave's own ring: ordered by its own vmcnt wait alone
             const uint8_t *wp = smem + kWRing + wave * 3072 + wq;
-            if constexpr (BITS == 4) {
+            if constexpr (FRAG) {   // w[2h] = half h's word of column block 0, w[2h + 1] = of column block 1
+                const uint32_t *wf = reinterpret_cast<const uint32_t *>(wp + wfrag);
+                w[0] = wf[0]; w[1] = wf[64];
+                w[2] = wf[2]; w[3] = wf[66];
+            } else if constexpr (BITS == 4) {
                 const uint4 v = *reinterpret_cast<const uint4 *>(wp + lane * 16);
                 w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
             } else {
@@ -641,13 +665,20 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
     };
     // A fragments of half h (words 2h, 2h + 1) for column blocks 0 and 1
     auto make_a = [&](int h, half8_t &c0, half8_t &c1) __attribute__((always_inline)) {
+        if constexpr (FRAG) {   // the words are the fragments' own: one dequant each, no regrouping
+            c0 = dequant_exact<BITS>(w, 2 * h, ec);
+            c1 = dequant_exact<BITS>(w, 2 * h + 1, ec1);
+            return;
+        }
         u32x4_t u0 = __builtin_bit_cast(u32x4_t, dequant_exact<BITS>(w, 2 * h, ec));
         u32x4_t u1 = __builtin_bit_cast(u32x4_t, dequant_exact<BITS>(w, 2 * h + 1, ec));
+        if constexpr (!NOSWAP) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const auto r = __builtin_amdgcn_permlane16_swap(u0[e], u1[e], false, false);
-            u0[e] = r[0];
-            u1[e] = r[1];
+            for (int e = 0; e < 4; ++e) {
+                const auto r = __builtin_amdgcn_permlane16_swap(u0[e], u1[e], false, false);
+                u0[e] = r[0];
+                u1[e] = r[1];
+            }
         }
         c0 = __builtin_bit_cast(half8_t, u0);
         c1 = __builtin_bit_cast(half8_t, u1);
@@ -856,8 +887,18 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
             load_w(sb, 0, GF ? 0 : 1);   // the k-step's parity
             if constexpr (GF) {
                 half2_t nz, sc;
-                split_sz(*reinterpret_cast<const uint32_t *>(sb + kGOff + (wave * 32 + (lane & 31)) * 4), nz, sc);
-                ec = exact_consts(nz);
+                if constexpr (FRAG) {   // columns i and 16 + i of the wave's 32
+                    const uint32_t *zl = reinterpret_cast<const uint32_t *>(sb + kGOff) + wave * 32 + row16;
+                    split_sz(zl[0], nz, sc);
+                    ec = exact_consts(nz);
+                    split_sz(zl[16], nz, sc);
+                    ec1 = exact_consts(nz);
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) ec1.magic[i] = ec.magic[i];   // one set of magic registers
+                } else {
+                    split_sz(*reinterpret_cast<const uint32_t *>(sb + kGOff + (wave * 32 + (lane & 31)) * 4), nz, sc);
+                    ec = exact_consts(nz);
+                }
                 const float *rl = reinterpret_cast<const float *>(sb + kGOff + 1024) + wave * 32 + 4 * rq;
                 r4[0] = *reinterpret_cast<const float4 *>(rl);
                 r4[1] = *reinterpret_cast<const float4 *>(rl + 16);
@@ -1029,11 +1070,17 @@ wq_horner16_kernel(const __half *__restrict__ X, int M, int K, const uint32_t *_
 
 // The three schedules of the 256-token kernel (A/B: profiles/horner16_ring4/): the 3-slot ring with
 // two barriers per k-step and the stagger; the 4-slot ring (MODE bit 13) with one barrier per k-step,
-// waves in lockstep; the 4-slot ring with waves 4-7 half a k-step behind.  All three give the same bits.
+// waves in lockstep; the 4-slot ring with waves 4-7 half a k-step behind.  All three give the same bits,
+// and so does the skewed ring with the A-fragment words read in fragment order (MODE bit 14; A/B:
+// profiles/horner16_tail/).
 [[maybe_unused]] constexpr int kH16Ring3 = 1 | 256 | 1024;
 [[maybe_unused]] constexpr int kH16Ring4 = 256 | 1024 | 8192;
 [[maybe_unused]] constexpr int kH16Ring4Skew = 1 | 256 | 1024 | 8192;
-constexpr int kH16Arm = kH16Ring4Skew;   // the product
+[[maybe_unused]] constexpr int kH16Ring4SkewFrag = kH16Ring4Skew | 16384;
+#ifndef DLLM_H16_ARM   // (an A/B build of the product ABI may name another schedule: make variant VFLAGS=-DDLLM_H16_ARM=..)
+#define DLLM_H16_ARM kH16Ring4SkewFrag
+#endif
+constexpr int kH16Arm = DLLM_H16_ARM;   // the product
 
 template <int MODE, int TB = 16, int BITS = 4>
 void launch_horner16_t(const HornerGemmArgs &a, int y_f32, hipStream_t st) {

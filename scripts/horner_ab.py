@@ -3,7 +3,10 @@ interleaved rounds, HIP events): -1 = the product kernel (linear_horner.hip, sta
 k-steps), 25 = the same without the stagger, 24 = round 2's wq_gemm8_kernel<..., HORNER>.
 All three run the same arithmetic in the same order, so their outputs must be bit-identical.
 The 256-token kernel's three schedules: 346 = 4-slot ring in lockstep, 347 = 4-slot ring with the skew
-(the product), 348 = 3-slot ring with a barrier every half k-step (profiles/horner16_ring4/)."""
+(the product until the fragment-order reads), 348 = 3-slot ring with a barrier every half k-step
+(profiles/horner16_ring4/).  The A-fragment words of the skewed ring (profiles/horner16_tail/): 347 = read as
+stored, regrouped by lane swaps; 349 = the same with the swaps dropped (results wrong, timing only);
+350 = read in fragment order, no swaps (the product)."""
 import json
 import os
 import sys
