@@ -1,4 +1,4 @@
-// capi.cpp -- library-level C-ABI entry points (errors, version, device probe).
+// capi.cpp -- library-level C-ABI entry points (version, device probe) and the device workspaces.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,17 +10,9 @@
 #include <vector>
 
 #include "dllm_quant.h"
+#include "error.hpp"
 
 namespace dllm {
-
-static thread_local std::string g_last_error;
-
-void set_error(const std::string &msg) { g_last_error = msg; }
-
-int fail(int code, const std::string &msg) {
-    g_last_error = msg;
-    return code;
-}
 
 // Grow-only per-(device, stream, slot) workspaces.  A buffer handed out while its stream was being
 // captured is referenced by that graph for as long as the graph lives, so once captured it is never
@@ -97,8 +89,6 @@ unsigned *zeroed_counters(hipStream_t st, size_t n) {
 }  // namespace dllm
 
 extern "C" {
-
-const char *dllm_last_error(void) { return dllm::g_last_error.c_str(); }
 
 const char *dllm_version(void) { return "dllm_hip 0.1.0 (gfx950)"; }
 

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "dllm_quant.h"
+#include "error.hpp"         // set_error, fail: the message behind dllm_last_error()
 #include "plan_consts.hpp"   // kWave, kCUs, kXCDs and the linear layer's host-visible constants
 
 // Streaming (non-temporal) stores for the GEMMs' f16 tile rows (whole 512-B rows per instruction;
@@ -19,10 +20,6 @@
 #endif
 
 namespace dllm {
-
-// Thread-local error message behind dllm_last_error().
-void set_error(const std::string &msg);
-int fail(int code, const std::string &msg);
 
 #define DLLM_HIP_TRY(expr)                                                                        \
     do {                                                                                          \

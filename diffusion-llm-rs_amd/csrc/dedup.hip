@@ -3,7 +3,7 @@
 // kept rows together.  The write path between dllm_compress_vectors and the search scan.
 //
 // The three rules (hash, filter, merge) are pinned in include/dllm_quant.h, section 8i; this file is
-// their device form, capi_host.cpp's dllm_*_host entries the serial C++ mirror and tests/dedup_ref.py
+// their device form, host_rules.cpp's dllm_*_host entries the serial C++ mirror and tests/dedup_ref.py
 // two Python restatements.  Everything is integer arithmetic: all of them agree to the bit.
 //   dedup_hash_kernel<G>   the hot path: one read of the codes.  G lanes (4, 16 or 64) share a row;
 //                          a lane takes aligned 16-byte pieces, folds each to its base-31 value,
@@ -35,8 +35,6 @@ constexpr int kThreads = 256;
 constexpr int kRowsPerThread = 4;
 constexpr int kBlockRows = kThreads * kRowsPerThread;   // rows per resolve / scatter workgroup
 constexpr int kScanThreads = 1024;
-constexpr size_t kMaxRows = size_t(1) << 31;
-constexpr size_t kMaxSeq = size_t(1) << 62;
 
 // ---- rule 1: the hash ------------------------------------------------------------------------------
 
@@ -397,12 +395,6 @@ inline size_t oneshot_slots(size_t rows) {
     return s;
 }
 
-int check_dim(size_t dim, size_t ld) {
-    if (dim == 0 || dim > kMaxDim) return fail(DLLM_ERR_INVALID_PARAMS, "dim must be between 1 and 65535");
-    if (ld < dim) return fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least dim");
-    return DLLM_OK;
-}
-
 }  // namespace
 }  // namespace dllm
 
@@ -411,8 +403,7 @@ using namespace dllm;
 extern "C" {
 
 int dllm_hash_rows(const uint8_t *codes, size_t rows, size_t dim, size_t ld, uint64_t *hashes, dllm_stream_t stream) {
-    if (int rc = check_dim(dim, ld)) return rc;
-    if (rows >= kMaxRows) return fail(DLLM_ERR_SHAPE_MISMATCH, "rows must be below 2^31");
+    if (int rc = check_hash_args(rows, dim, ld)) return rc;
     if (rows == 0) return DLLM_OK;
     if (!codes || !hashes) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
     if (reinterpret_cast<uintptr_t>(hashes) % 8) return fail(DLLM_ERR_INVALID_PARAMS, "hashes must be 8-byte aligned");
@@ -434,15 +425,10 @@ int dllm_hash_rows(const uint8_t *codes, size_t rows, size_t dim, size_t ld, uin
     return DLLM_OK;
 }
 
-size_t dllm_dedup_table_bytes(size_t slots) {
-    if (!is_pow2(slots) || slots > (size_t(1) << 56)) return 0;
-    return table_words(slots) * sizeof(uint64_t);
-}
-
 int dllm_dedup_table_init(void *table, size_t slots, dllm_stream_t stream) {
-    if (!dllm_dedup_table_bytes(slots)) return fail(DLLM_ERR_INVALID_PARAMS, "slots must be a power of two");
+    if (int rc = check_slots(slots)) return rc;
     if (!table) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
-    if (reinterpret_cast<uintptr_t>(table) % 8) return fail(DLLM_ERR_INVALID_PARAMS, "table must be 8-byte aligned");
+    if (int rc = check_table_aligned(table)) return rc;
     const size_t words = table_words(slots);
     dedup_init_kernel<<<grid_for(words, kThreads), kThreads, 0, as_stream(stream)>>>(static_cast<uint64_t *>(table), words);
     DLLM_LAUNCH_CHECK();
@@ -457,14 +443,7 @@ size_t dllm_dedup_workspace(size_t rows) {
 int dllm_dedup_rows(const uint64_t *hashes, size_t rows, uint64_t base, void *table, size_t slots, uint8_t *keep,
                     uint64_t *first, int32_t *kept_rows, uint32_t *n_kept, void *workspace, size_t workspace_bytes,
                     dllm_stream_t stream) {
-    if (rows >= kMaxRows) return fail(DLLM_ERR_SHAPE_MISMATCH, "rows must be below 2^31 (a kept row's index is an int32)");
-    if (base >= kMaxSeq) return fail(DLLM_ERR_INVALID_PARAMS, "base must be below 2^62");
-    if (table) {
-        if (!dllm_dedup_table_bytes(slots)) return fail(DLLM_ERR_INVALID_PARAMS, "slots must be a power of two");
-        if (reinterpret_cast<uintptr_t>(table) % 8) return fail(DLLM_ERR_INVALID_PARAMS, "table must be 8-byte aligned");
-        if (base + rows > slots / 2)
-            return fail(DLLM_ERR_INVALID_PARAMS, "base + rows exceeds slots / 2: the seen-set is kept at most half full");
-    }
+    if (int rc = check_filter_args(rows, base, table, slots)) return rc;
     if (rows == 0) return DLLM_OK;
     if (!hashes || !keep || !first || !kept_rows || !n_kept) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
     if (!workspace || workspace_bytes < dllm_dedup_workspace(rows))
@@ -497,8 +476,7 @@ int dllm_dedup_rows(const uint64_t *hashes, size_t rows, uint64_t base, void *ta
 
 int dllm_gather_rows(const uint8_t *codes, size_t dim, size_t ld, const int32_t *kept_rows, const uint32_t *n_kept,
                      uint8_t *out, size_t out_ld, dllm_stream_t stream) {
-    if (int rc = check_dim(dim, ld)) return rc;
-    if (out_ld < dim) return fail(DLLM_ERR_INVALID_PARAMS, "out_ld must be at least dim");
+    if (int rc = check_gather_args(dim, ld, out_ld)) return rc;
     if (!codes || !kept_rows || !n_kept || !out) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
     if (reinterpret_cast<uintptr_t>(kept_rows) % 4 || reinterpret_cast<uintptr_t>(n_kept) % 4)
         return fail(DLLM_ERR_INVALID_PARAMS, "kept_rows and n_kept must be 4-byte aligned");

@@ -1,5 +1,5 @@
 // dedup_rule.hpp -- the constants of the dedup rules (include/dllm_quant.h 8i) shared by the kernels
-// of dedup.hip and the host mirror in capi_host.cpp (plain C++: usable without HIP).
+// of dedup.hip and the host mirror in host_rules.cpp (plain C++: usable without HIP).
 //
 // The seen-set is one array of u64 words in caller-owned memory:
 //   word 0        flag: nonzero once a row found no slot (only a dishonest `base` gets there)
@@ -15,11 +15,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define DLLM_DEDUP_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define DLLM_DEDUP_HD inline
-#endif
+#include "search_rule.hpp"   // the store's limits (dim, rows)
 
 namespace dllm {
 namespace dedup {
@@ -28,14 +24,17 @@ constexpr uint64_t kEmptyKey = ~uint64_t(0);
 constexpr uint64_t kNoSeq = ~uint64_t(0);
 constexpr size_t kHeaderWords = 4;
 constexpr size_t kFlagWord = 0, kCountWord = 1, kSideWord = 2;
-constexpr size_t kMaxDim = 65535;
+using search::kMaxDim;
+using search::kMaxRows;
+constexpr uint64_t kMaxSeq = uint64_t(1) << 62;   // sequence numbers (base + row) stay below it
+constexpr size_t kMaxSlots = size_t(1) << 56;
 
 constexpr bool is_pow2(size_t n) { return n != 0 && (n & (n - 1)) == 0; }
 constexpr size_t table_words(size_t slots) { return kHeaderWords + 2 * slots; }
 
 // The slot a probe starts at.  The hash's low bits are a short sum of the last few codes (31^k b),
 // so they are mixed with the high ones first: a multiply by 2^64 / phi, the high word folded down.
-DLLM_DEDUP_HD size_t first_slot(uint64_t h, size_t mask) {
+DLLM_HD size_t first_slot(uint64_t h, size_t mask) {
     uint64_t m = h * 0x9E3779B97F4A7C15ull;
     m ^= m >> 32;
     return static_cast<size_t>(m) & mask;
@@ -58,6 +57,52 @@ constexpr uint64_t inv31() {
     return x;
 }
 static_assert(inv31() * 31 == 1, "inverse of 31 mod 2^64");
+
+// ---- argument checks: the device entry point and its _host twin call the same function (static: a
+// translation unit's own copy, so the library exports none of them) ----
+
+constexpr bool slots_ok(size_t slots) { return is_pow2(slots) && slots <= kMaxSlots; }
+
+static inline int check_dim(size_t dim, size_t ld) {
+    if (dim == 0 || dim > kMaxDim) return fail(DLLM_ERR_INVALID_PARAMS, "dim must be between 1 and 65535");
+    if (ld < dim) return fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least dim");
+    return DLLM_OK;
+}
+
+static inline int check_hash_args(size_t rows, size_t dim, size_t ld) {
+    if (int rc = check_dim(dim, ld)) return rc;
+    if (rows >= kMaxRows) return fail(DLLM_ERR_SHAPE_MISMATCH, "rows must be below 2^31");
+    return DLLM_OK;
+}
+
+static inline int check_slots(size_t slots) {
+    if (!slots_ok(slots)) return fail(DLLM_ERR_INVALID_PARAMS, "slots must be a power of two");
+    return DLLM_OK;
+}
+
+static inline int check_table_aligned(const void *table) {
+    if (reinterpret_cast<uintptr_t>(table) % 8) return fail(DLLM_ERR_INVALID_PARAMS, "table must be 8-byte aligned");
+    return DLLM_OK;
+}
+
+// The values of dllm_dedup_rows, before its "rows == 0: nothing to do"; table == null is the one-shot form.
+static inline int check_filter_args(size_t rows, uint64_t base, const void *table, size_t slots) {
+    if (rows >= kMaxRows) return fail(DLLM_ERR_SHAPE_MISMATCH, "rows must be below 2^31 (a kept row's index is an int32)");
+    if (base >= kMaxSeq) return fail(DLLM_ERR_INVALID_PARAMS, "base must be below 2^62");
+    if (table) {
+        if (int rc = check_slots(slots)) return rc;
+        if (int rc = check_table_aligned(table)) return rc;
+        if (base + rows > slots / 2)
+            return fail(DLLM_ERR_INVALID_PARAMS, "base + rows exceeds slots / 2: the seen-set is kept at most half full");
+    }
+    return DLLM_OK;
+}
+
+static inline int check_gather_args(size_t dim, size_t ld, size_t out_ld) {
+    if (int rc = check_dim(dim, ld)) return rc;
+    if (out_ld < dim) return fail(DLLM_ERR_INVALID_PARAMS, "out_ld must be at least dim");
+    return DLLM_OK;
+}
 
 }  // namespace dedup
 }  // namespace dllm

@@ -4,7 +4,7 @@
 // is the consumer.
 //
 // The rule (pair table, score, drops, key order) is pinned in include/dllm_quant.h 8l and its
-// arithmetic lives in neighbor_rule.hpp; capi_host.cpp's dllm_neighbor_*_host is the plain C++ mirror
+// arithmetic lives in neighbor_rule.hpp; host_rules.cpp's dllm_neighbor_*_host is the plain C++ mirror
 // and tests/neighbors_ref.py the numpy restatement.  All on the caller's stream, no atomics, no
 // allocation:
 //   neighbor_table_kernel  a wave per kTableRows rows: C1, C2 (exact u32), the f64 norm, (a, b, C1)
@@ -230,12 +230,6 @@ NeighborPlan neighbor_plan(size_t nq, size_t rows, size_t k) {
     return p;
 }
 
-int check_store_shape(size_t rows, size_t dim) {
-    if (dim == 0 || dim > neighbor::kMaxDim) return fail(DLLM_ERR_INVALID_PARAMS, "dim must be between 1 and 65535");
-    if (rows >= (size_t(1) << 31)) return fail(DLLM_ERR_SHAPE_MISMATCH, "rows must be below 2^31 (the index is an int32)");
-    return DLLM_OK;
-}
-
 template <int VEC>
 void launch_scan(dim3 grid, hipStream_t st, const uint8_t *qcodes, const Entry *qtable, size_t nq, const uint8_t *codes,
                  const Entry *table, size_t rows, size_t dim, float threshold, int64_t self_base, size_t j0, float *sc) {
@@ -250,16 +244,14 @@ using namespace dllm;
 
 extern "C" {
 
-size_t dllm_neighbor_table_bytes(size_t rows) { return rows * sizeof(Entry); }
-
 size_t dllm_neighbor_workspace(size_t nq, size_t rows, size_t k) { return neighbor_plan(nq, rows, k).total; }
 
 int dllm_neighbor_table(const uint8_t *codes, size_t rows, size_t dim, const float *scales, const float *zps, void *table,
                         dllm_stream_t stream) {
-    if (int rc = check_store_shape(rows, dim)) return rc;
+    if (int rc = search::check_store_shape(rows, dim)) return rc;
     if (rows == 0) return DLLM_OK;
     if (!codes || !scales || !zps || !table) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
-    if (reinterpret_cast<uintptr_t>(table) % 8) return fail(DLLM_ERR_INVALID_PARAMS, "table must be 8-byte aligned");
+    if (int rc = neighbor::check_table_aligned(table)) return rc;
     const int aligned = dim % 4 == 0 && reinterpret_cast<uintptr_t>(codes) % 4 == 0;
     const unsigned grid = static_cast<unsigned>((rows + kTableWaves * kTableRows - 1) / (kTableWaves * kTableRows));
     neighbor_table_kernel<<<grid, kTableWaves * kWaveLanes, 0, as_stream(stream)>>>(codes, rows, dim, scales, zps, aligned,
@@ -271,17 +263,9 @@ int dllm_neighbor_table(const uint8_t *codes, size_t rows, size_t dim, const flo
 int dllm_neighbor_rows(const uint8_t *qcodes, const void *qtable, size_t nq, const uint8_t *codes, const void *table,
                        size_t rows, size_t dim, size_t k, float threshold, int64_t self_base, int32_t *idx, float *scores,
                        void *workspace, size_t workspace_bytes, dllm_stream_t stream) {
-    if (k == 0 || k > neighbor::kMaxK) return fail(DLLM_ERR_INVALID_PARAMS, "k must be between 1 and 256");
-    if (int rc = check_store_shape(rows, dim)) return rc;
-    if (threshold != threshold) return fail(DLLM_ERR_INVALID_PARAMS, "threshold must not be NaN");
-    if (self_base < -1) return fail(DLLM_ERR_INVALID_PARAMS, "self_base must be -1 or a row of the store");
-    if (self_base >= 0 && (static_cast<uint64_t>(self_base) > rows || nq > rows - static_cast<uint64_t>(self_base)))
-        return fail(DLLM_ERR_INVALID_PARAMS, "self_base + nq exceeds rows");
+    if (int rc = neighbor::check_rows_args(nq, rows, dim, k, threshold, self_base)) return rc;
     if (nq == 0) return DLLM_OK;
-    if (!qcodes || !qtable || !idx || !scores || (rows && (!codes || !table)))
-        return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
-    if (reinterpret_cast<uintptr_t>(qtable) % 8 || reinterpret_cast<uintptr_t>(table) % 8)
-        return fail(DLLM_ERR_INVALID_PARAMS, "qtable and table must be 8-byte aligned");
+    if (int rc = neighbor::check_rows_buffers(qcodes, qtable, codes, table, rows, idx, scores)) return rc;
     hipStream_t st = as_stream(stream);
     if (rows == 0) return select_fill_empty(nq * k, idx, scores, st);
     const NeighborPlan plan = neighbor_plan(nq, rows, k);

@@ -3,7 +3,7 @@
 // one consumer of dllm_compress_vectors' output that reads it on the device.
 //
 // The score rule (strand sums, row table, key order) is pinned in include/dllm_quant.h; this file
-// is its device form, capi_host.cpp's dllm_search_*_host its plain C++ mirror and
+// is its device form, host_rules.cpp's dllm_search_*_host its plain C++ mirror and
 // tests/search_ref.py its numpy restatement.  Four kernels, all on the caller's stream, no atomics,
 // no allocation:
 //   search_table_kernel   a wave per kTableRows rows: C1 = sum c, C2 = sum c^2 (exact u32), the f64 norm, (u, v)
@@ -18,12 +18,15 @@
 //
 // Reference: diffusion_prefill/src/fusion_ann.rs:109-136 (cosine, sort descending, take k).
 #include "common.hpp"
+#include "search_rule.hpp"
 #include "search_select.hpp"
 
 #include <cmath>
 
 namespace dllm {
 namespace {
+
+using search::search_key;   // the key order: search_rule.hpp
 
 constexpr int kStrands = 64;            // = the wave: lane l owns the codes d with (d / 4) % 64 == l
 constexpr int kTripBytes = 4 * kStrands;
@@ -34,8 +37,6 @@ constexpr int kScanThreads = kScanWaves * kStrands;
 constexpr int kScanTile = 4;            // queries held in registers per pass over the codes
 constexpr int kSlice = 2048;            // keys one select workgroup sorts in LDS (16 KiB)
 constexpr int kSelThreads = 256;
-constexpr unsigned kMaxK = 256;
-constexpr size_t kMaxDim = 65535;
 
 // a[i] = a[i] + a[i ^ m], m = 32 .. 1: every lane ends with the strand tree's root.
 __device__ __forceinline__ float strand_tree(float a) {
@@ -251,21 +252,6 @@ __global__ void __launch_bounds__(kScanThreads) search_scan_kernel(const float *
 
 // ---- select ----------------------------------------------------------------------------------------
 
-// (score descending, index ascending) as one u64 ascending: the score's bits made orderable in the
-// high word (-0 folded into +0, every NaN below -inf), the complemented index in the low word.
-// Index < 2^31 keeps the low word >= 2^31, so the key 0 is free to mean "no row".
-__device__ __forceinline__ uint64_t search_key(float s, uint32_t idx) {
-    uint32_t b = __float_as_uint(s);
-    uint32_t ord;
-    if (s != s) {
-        ord = 0u;
-    } else {
-        if (b == 0x80000000u) b = 0u;
-        ord = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    return (static_cast<uint64_t>(ord) << 32) | static_cast<uint32_t>(~idx);
-}
-
 // One stage of the bitonic network over s[0, len): element lo against lo | jj, the larger first
 // where (lo & kk) == 0.  A thread's pairs are all read, then all written (taken one pair at a time,
 // each LDS round trip would wait for the one before it).  Ends with a barrier.
@@ -407,12 +393,6 @@ void launch_scan(bool aligned, dim3 grid, hipStream_t st, const float *Q, const 
         search_scan_kernel<TQ, false><<<grid, kScanThreads, 0, st>>>(Q, codes, table, qstat, rows, dim, j0, scores);
 }
 
-int check_store_shape(size_t rows, size_t dim) {
-    if (dim == 0 || dim > kMaxDim) return fail(DLLM_ERR_INVALID_PARAMS, "dim must be between 1 and 65535");
-    if (rows >= (size_t(1) << 31)) return fail(DLLM_ERR_SHAPE_MISMATCH, "rows must be below 2^31 (the index is an int32)");
-    return DLLM_OK;
-}
-
 }  // namespace
 
 SelectPlan select_plan(size_t nq, size_t rows, size_t k) {
@@ -467,7 +447,7 @@ size_t dllm_search_workspace(size_t nq, size_t rows, size_t k) { return search_p
 
 int dllm_search_table(const uint8_t *codes, size_t rows, size_t dim, const float *scales, const float *zps,
                       float *table, dllm_stream_t stream) {
-    if (int rc = check_store_shape(rows, dim)) return rc;
+    if (int rc = search::check_store_shape(rows, dim)) return rc;
     if (rows == 0) return DLLM_OK;
     if (!codes || !scales || !zps || !table) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
     const int aligned = dim % 4 == 0 && reinterpret_cast<uintptr_t>(codes) % 4 == 0;
@@ -480,8 +460,8 @@ int dllm_search_table(const uint8_t *codes, size_t rows, size_t dim, const float
 int dllm_search_vectors(const float *Q, size_t nq, const uint8_t *codes, const float *table, size_t rows, size_t dim,
                         size_t k, int32_t *idx, float *scores, void *workspace, size_t workspace_bytes,
                         dllm_stream_t stream) {
-    if (k == 0 || k > kMaxK) return fail(DLLM_ERR_INVALID_PARAMS, "k must be between 1 and 256");
-    if (int rc = check_store_shape(rows, dim)) return rc;
+    if (int rc = search::check_k(k)) return rc;
+    if (int rc = search::check_store_shape(rows, dim)) return rc;
     if (nq == 0) return DLLM_OK;
     if (!Q || !idx || !scores || (rows && (!codes || !table))) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
     hipStream_t st = as_stream(stream);

@@ -19,6 +19,7 @@
 //                        radix select over u64 weight sums; the combined tau replaces the select's
 // No global atomics, no allocation, no synchronisation.
 #include "common.hpp"
+#include "token_args.hpp"
 #include "token_exp.hpp"
 #include "token_nucleus_rule.hpp"
 #include "token_sample_rule.hpp"
@@ -30,7 +31,7 @@ namespace {
 
 constexpr int kTokLanes = 256;                         // lanes of a chunk = threads of a block
 constexpr int kTokTrips = 16;                          // groups of four per lane and chunk
-constexpr size_t kTokChunk = 4 * kTokLanes * kTokTrips;    // 16384 elements
+static_assert(kTokChunk == 4 * kTokLanes * kTokTrips, "a chunk (token_args.hpp) is 16384 elements");
 constexpr int kTokWaves = kTokLanes / 64;
 
 inline size_t tok_chunks(size_t V) { return (V + kTokChunk - 1) / kTokChunk; }
@@ -839,10 +840,7 @@ size_t dllm_token_readout_workspace(size_t M, size_t V) { return M * tok_chunks(
 
 int dllm_token_readout(const void *logits, int dtype, size_t M, size_t V, size_t ld, int32_t *tokens, float *stats,
                        float *probs, void *workspace, size_t workspace_bytes, dllm_stream_t stream) {
-    if (V == 0) return fail(DLLM_ERR_INVALID_PARAMS, "V == 0: no token to read out of an empty vocabulary");
-    if (ld < V) return fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least V");
-    if (V >= (size_t(1) << 31)) return fail(DLLM_ERR_SHAPE_MISMATCH, "V must be below 2^31 (the token is an int32)");
-    if (dtype != DLLM_F32 && dtype != DLLM_F16) return fail(DLLM_ERR_UNSUPPORTED, "dtype must be DLLM_F32 or DLLM_F16");
+    if (int rc = token::check_logits(V, ld, dtype, false)) return rc;
     if (M == 0) return DLLM_OK;
     if (!logits || !tokens || !stats || !workspace) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
     if (reinterpret_cast<uintptr_t>(workspace) % 4)
@@ -939,13 +937,8 @@ extern "C" {
 int dllm_token_sample(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature, size_t top_k,
                       const float *u, uint64_t seed, uint64_t offset, int32_t *tokens, float *stats, void *workspace,
                       size_t workspace_bytes, dllm_stream_t stream) {
-    if (V == 0) return fail(DLLM_ERR_INVALID_PARAMS, "V == 0: no token to sample from an empty vocabulary");
-    if (ld < V) return fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least V");
-    if (V >= (size_t(1) << 31)) return fail(DLLM_ERR_SHAPE_MISMATCH, "V must be below 2^31 (the token is an int32)");
-    if (dtype != DLLM_F32 && dtype != DLLM_F16) return fail(DLLM_ERR_UNSUPPORTED, "dtype must be DLLM_F32 or DLLM_F16");
-    const float r = 1.0f / temperature;                 // 8j.1: one IEEE division
-    if (!(temperature > 0.0f) || !std::isfinite(temperature) || !std::isfinite(r))
-        return fail(DLLM_ERR_INVALID_PARAMS, "temperature and 1 / temperature must be positive and finite");
+    float r;
+    if (int rc = token::check_sample_args(V, ld, dtype, temperature, r)) return rc;
     if (M == 0) return DLLM_OK;
     if (!logits || !tokens || !stats || !workspace) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
     if (reinterpret_cast<uintptr_t>(workspace) % 4)
@@ -960,15 +953,8 @@ int dllm_token_sample(const void *logits, int dtype, size_t M, size_t V, size_t 
 int dllm_token_sample_ex(const void *logits, int dtype, size_t M, size_t V, size_t ld, float temperature, size_t top_k,
                          float top_p, float min_p, const float *u, uint64_t seed, uint64_t offset, int32_t *tokens,
                          float *stats, void *workspace, size_t workspace_bytes, dllm_stream_t stream) {
-    if (V == 0) return fail(DLLM_ERR_INVALID_PARAMS, "V == 0: no token to sample from an empty vocabulary");
-    if (ld < V) return fail(DLLM_ERR_INVALID_PARAMS, "ld must be at least V");
-    if (V >= (size_t(1) << 31)) return fail(DLLM_ERR_SHAPE_MISMATCH, "V must be below 2^31 (the token is an int32)");
-    if (dtype != DLLM_F32 && dtype != DLLM_F16) return fail(DLLM_ERR_UNSUPPORTED, "dtype must be DLLM_F32 or DLLM_F16");
-    const float r = 1.0f / temperature;                 // 8j.1: one IEEE division
-    if (!(temperature > 0.0f) || !std::isfinite(temperature) || !std::isfinite(r))
-        return fail(DLLM_ERR_INVALID_PARAMS, "temperature and 1 / temperature must be positive and finite");
-    if (!(top_p > 0.0f) || top_p > 1.0f) return fail(DLLM_ERR_INVALID_PARAMS, "top_p must be in (0, 1]");
-    if (!(min_p >= 0.0f) || min_p > 1.0f) return fail(DLLM_ERR_INVALID_PARAMS, "min_p must be in [0, 1]");
+    float r;
+    if (int rc = token::check_sample_ex_args(V, ld, dtype, temperature, top_p, min_p, r)) return rc;
     if (M == 0) return DLLM_OK;
     if (!logits || !tokens || !stats || !workspace) return fail(DLLM_ERR_INVALID_PARAMS, "NULL argument");
     if (reinterpret_cast<uintptr_t>(workspace) % 4)

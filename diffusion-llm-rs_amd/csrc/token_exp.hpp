@@ -1,5 +1,5 @@
 // token_exp.hpp -- EXP, the f32 exponential of the token readout (include/dllm_quant.h 8h), shared
-// by the kernels of token.hip and the host mirror in capi_host.cpp (and usable without HIP: the
+// by the kernels of token.hip and the host mirror in host_rules.cpp (and usable without HIP: the
 // exhaustive check tests/cpp/token_host_check.cpp includes it from a plain C++ program).
 //
 // Domain: d <= 0, -inf and NaN.  Built only from f32 add, multiply and fmaf (each rounded once;
@@ -28,11 +28,7 @@
 
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define DLLM_TOKEN_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define DLLM_TOKEN_HD inline
-#endif
+#include "rule_hd.hpp"
 
 namespace dllm {
 namespace token {
@@ -45,7 +41,7 @@ constexpr float kExpUlps = 0.9371f;
 // The body for d in [-87, 0] (callers handle NaN and the cut-off).  On the device RN-to-integer and
 // the scaling are single instructions (v_rndne_f32, v_ldexp_f32) with the values of the two-add form
 // and of the multiply by 2^kf: both exact operations, the same bits.
-DLLM_TOKEN_HD float exp_body(float d) {
+DLLM_HD float exp_body(float d) {
     const float t = d * 0x1.715476p+0f;
 #if defined(__HIP_DEVICE_COMPILE__)
     const float kf = __builtin_rintf(t);
@@ -70,7 +66,7 @@ DLLM_TOKEN_HD float exp_body(float d) {
 #endif
 }
 
-DLLM_TOKEN_HD float exp_le0(float d) {
+DLLM_HD float exp_le0(float d) {
     if (d != d) return __builtin_bit_cast(float, 0x7fc00000u);
     if (d < kExpCut) return 0.0f;
     return exp_body(d);

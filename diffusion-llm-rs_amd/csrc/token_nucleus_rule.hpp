@@ -1,5 +1,5 @@
 // token_nucleus_rule.hpp -- the integer part of the top-p / min-p rule (include/dllm_quant.h 8k),
-// shared by the threshold search of token.hip and the host mirror in capi_host.cpp: the fixed-point
+// shared by the threshold search of token.hip and the host mirror in host_rules.cpp: the fixed-point
 // weight of an element, the fixed-point forms of the two parameters and the 96-bit comparison.
 //   W     = (u64) trunc(g * 2^32) for g = EXP(RN(y - m)) in [0, 1]: the product is exact (a power of two
 //           scales it), so W is an integer function of g's bits; W(1) = 2^32, W(+0) = 0.  EXP never
@@ -20,13 +20,13 @@ namespace dllm {
 namespace token {
 
 // 8k.2: the weight of an element from its g = EXP(RN(y - m)), 0 <= g <= 1.
-DLLM_TOKEN_HD uint64_t nucleus_weight(float g) {
+DLLM_HD uint64_t nucleus_weight(float g) {
     return g < 1.0f ? static_cast<uint64_t>(static_cast<uint32_t>(g * 0x1p32f)) : (uint64_t(1) << 32);
 }
 
 // 8k.3: does the mass A (of the elements >= a candidate threshold) reach the share pfix / 2^32 of T?
 // A 2^32 >= pfix T as 96-bit integers: the high words, then the low ones.
-DLLM_TOKEN_HD bool nucleus_reaches(uint64_t A, uint64_t pfix, uint64_t T) {
+DLLM_HD bool nucleus_reaches(uint64_t A, uint64_t pfix, uint64_t T) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint64_t hi = __umul64hi(pfix, T), lo = pfix * T;
     const uint64_t ahi = A >> 32, alo = A << 32;
@@ -40,7 +40,7 @@ DLLM_TOKEN_HD bool nucleus_reaches(uint64_t A, uint64_t pfix, uint64_t T) {
 // is reached by the maximum alone, whose weight is 2^32 >= 1; an element of weight 0 never decides).
 // A >= nucleus_need(pfix, T) is nucleus_reaches(A, pfix, T) for every A >= 1; the threshold search
 // computes it once per row and compares 64-bit sums against it.
-DLLM_TOKEN_HD uint64_t nucleus_need(uint64_t pfix, uint64_t T) {
+DLLM_HD uint64_t nucleus_need(uint64_t pfix, uint64_t T) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint64_t hi = __umul64hi(pfix, T), lo = pfix * T;
 #else

@@ -1,5 +1,5 @@
 // token_sample_rule.hpp -- the integer part of the token sampling rule (include/dllm_quant.h 8j.4),
-// shared by the kernels of token.hip and the host mirror in capi_host.cpp: the three uniforms of a
+// shared by the kernels of token.hip and the host mirror in host_rules.cpp: the three uniforms of a
 // row.  Philox4x32-10 keyed by (seed lo, seed hi) on the counter (i lo, i hi, 1, 0); the 1 in the
 // third word keeps these draws apart from the N(0,1) stream of csrc/diffusion_rng.hpp, whose
 // counters are (blk lo, blk hi, 0, 0).  u_l = float(w_l >> 8) * 2^-24: a 24-bit integer and a power
@@ -13,7 +13,7 @@
 namespace dllm {
 namespace token {
 
-DLLM_TOKEN_HD void sample_uniforms(uint64_t seed, uint64_t i, float (&u)[3]) {
+DLLM_HD void sample_uniforms(uint64_t seed, uint64_t i, float (&u)[3]) {
     uint32_t c0 = static_cast<uint32_t>(i), c1 = static_cast<uint32_t>(i >> 32), c2 = 1u, c3 = 0u;
     uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
     for (int r = 0; r < 10; ++r) {

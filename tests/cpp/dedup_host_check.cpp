@@ -1,6 +1,6 @@
 // dedup_host_check.cpp -- a stand-alone driver (its own main) of the host dedup entry points
 // (dllm_hash_rows_host, dllm_dedup_table_init_host, dllm_dedup_rows_host, dllm_gather_rows_host,
-// csrc/capi_host.cpp), meant to be compiled together with capi_host.cpp under the address and
+// csrc/host_rules.cpp), meant to be compiled together with host_rules.cpp under the address and
 // undefined-behaviour sanitizers and run on a CPU.  Every buffer is a heap allocation of exactly the
 // size the header states, so a read or write past an end is caught.  The values are checked against
 // forms that need no second implementation of the entry: the hash as a power-weighted sum, the filter

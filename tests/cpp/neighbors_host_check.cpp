@@ -1,6 +1,6 @@
 // neighbors_host_check.cpp -- a stand-alone driver of the host row-against-row entry points
-// (dllm_neighbor_table_host / dllm_neighbor_rows_host, csrc/capi_host.cpp), meant to be compiled
-// together with capi_host.cpp under the address and undefined-behaviour sanitizers and run on a
+// (dllm_neighbor_table_host / dllm_neighbor_rows_host, csrc/host_rules.cpp), meant to be compiled
+// together with host_rules.cpp under the address and undefined-behaviour sanitizers and run on a
 // CPU.  Every buffer is a heap allocation of exactly the size the header states, so a read or write
 // past an end is caught; the values are checked for what needs no second implementation: the
 // ranking order, the dropped self pair, the -1 / -inf tail, slice invariance, symmetry and the

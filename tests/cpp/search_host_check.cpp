@@ -1,6 +1,6 @@
 // search_host_check.cpp -- a stand-alone driver of the host search entry points
-// (dllm_search_table_host / dllm_search_vectors_host, csrc/capi_host.cpp), meant to be compiled
-// together with capi_host.cpp under the address and undefined-behaviour sanitizers and run on a
+// (dllm_search_table_host / dllm_search_vectors_host, csrc/host_rules.cpp), meant to be compiled
+// together with host_rules.cpp under the address and undefined-behaviour sanitizers and run on a
 // CPU.  Every buffer is a heap allocation of exactly the size the header states, so a read or write
 // past an end is caught; the values are checked for what needs no second implementation: the
 // ranking order, slice invariance, the -1 / -inf tail and the rejections.

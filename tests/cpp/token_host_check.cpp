@@ -1,7 +1,7 @@
 // token_host_check.cpp -- a stand-alone driver (its own main) of the token readout's host side.
 //
-//   token_host_check               dllm_token_readout_host (csrc/capi_host.cpp) on exact-size heap
-//                                  buffers, meant to be compiled with capi_host.cpp under the address
+//   token_host_check               dllm_token_readout_host (csrc/host_rules.cpp) on exact-size heap
+//                                  buffers, meant to be compiled with host_rules.cpp under the address
 //                                  and undefined-behaviour sanitizers: a read or write past an end is
 //                                  caught; the values are checked for what needs no second
 //                                  implementation (the literal fold, Z >= 1, sum p ~ 1, p_token = 1 / Z,

@@ -1,6 +1,6 @@
 // token_nucleus_host_check.cpp -- a stand-alone driver (its own main) of the host side of top-p / min-p
-// sampling: dllm_token_sample_ex_host (csrc/capi_host.cpp) on exact-size heap buffers, meant to be
-// compiled with capi_host.cpp under the address and undefined-behaviour sanitizers: a read or write
+// sampling: dllm_token_sample_ex_host (csrc/host_rules.cpp) on exact-size heap buffers, meant to be
+// compiled with host_rules.cpp under the address and undefined-behaviour sanitizers: a read or write
 // past an end is caught.  The values are checked for what needs no second implementation: with both
 // masks off the outputs are dllm_token_sample_host's; the token lies in the row and at or above tau;
 // tau is one of the row's values and never below the top-k threshold; the kept mass reaches the share

@@ -1,6 +1,6 @@
 // token_sample_host_check.cpp -- a stand-alone driver (its own main) of token sampling's host side:
-// dllm_token_sample_host (csrc/capi_host.cpp) on exact-size heap buffers, meant to be compiled with
-// capi_host.cpp under the address and undefined-behaviour sanitizers: a read or write past an end is
+// dllm_token_sample_host (csrc/host_rules.cpp) on exact-size heap buffers, meant to be compiled with
+// host_rules.cpp under the address and undefined-behaviour sanitizers: a read or write past an end is
 // caught.  The values are checked for what needs no second implementation: the token lies in the row
 // and survives the mask, Z >= 1, p_token = EXP(y_tok - m) / Z <= 1, {m, Z} do not depend on the
 // uniforms, the extreme uniforms give the first and the last live element, padding is never read,

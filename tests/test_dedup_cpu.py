@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests import dedup_ref as ref
+from tests.host_check import run_host_check
 
 # one byte; below, at and above a 16-byte piece; the 64- and 256-byte group edges; the default hidden
 # size and its odd neighbour; a second trip of a 64-lane group (1025); many trips; the largest dim.
@@ -269,28 +270,13 @@ def test_wrappers_exported(dllm):
 
 # ---- the host entry points under the sanitizers -----------------------------------------------------------
 
-def test_host_entry_points_under_sanitizers(dllm, tmp_path):
-    """tests/cpp/dedup_host_check.cpp (its own main) with csrc/capi_host.cpp, both compiled for the
-    host under the address and undefined-behaviour sanitizers and run as a program of its own, the
-    rest of the ABI from the built library: exact-size heap buffers at every kind of dim, rows that end
+def test_host_entry_points_under_sanitizers(tmp_path):
+    """tests/cpp/dedup_host_check.cpp (its own main) with csrc/host_rules.cpp and error.cpp, compiled by
+    g++ under the address and undefined-behaviour sanitizers (tests/host_check.py; no hipcc, no
+    library) and run as a program of its own: exact-size heap buffers at every kind of dim, rows that end
     at the buffer's last byte, the reserved key, a table filled through a dishonest base."""
-    import os
-    import subprocess
-    from pathlib import Path
-    root = Path(__file__).resolve().parents[1]
-    csrc = root / "diffusion-llm-rs_amd" / "csrc"
-    lib = dllm._lib.LIB_PATH.parent
-    exe = tmp_path / "dedup_host_check"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wno-option-ignored"]
-    cmd += [a for f in san for a in ("-Xarch_host", f)] + [san[0]]       # the last one links the runtimes
-    cmd += [f"-I{root / 'include'}", f"-I{csrc}", str(root / "tests" / "cpp" / "dedup_host_check.cpp"),
-            str(csrc / "capi_host.cpp"), f"-L{lib}", "-ldllm_hip", f"-Wl,-rpath,{lib}", "-o", str(exe)]
-    subprocess.run(cmd, check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
-    assert " 0 failed" in r.stdout
+    run_host_check("dedup_host_check", tmp_path, timeout=120)
+
 
 
 def test_cpp_mirror_dedup_buffer(dllm, tmp_path):

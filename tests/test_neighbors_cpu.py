@@ -13,6 +13,7 @@ import pytest
 
 from tests import neighbors_ref as ref
 from tests import search_ref
+from tests.host_check import run_host_check
 
 DIMS = [1, 3, 16, 63, 64, 65, 263, 768]
 NINF = -math.inf
@@ -364,24 +365,8 @@ def test_vector_index_graph_calls_with_device_stubbed(dllm, monkeypatch):
 
 # ---- the host entry points under the sanitizers -----------------------------------------------------
 
-def test_host_entry_points_under_sanitizers(dllm, tmp_path):
-    """tests/cpp/neighbors_host_check.cpp (its own main) with csrc/capi_host.cpp, both compiled for the
-    host under the address and undefined-behaviour sanitizers, the rest of the ABI from the built
-    library: exact-size heap buffers at every kind of dim, blocks from the start, middle and end."""
-    import os
-    import subprocess
-    from pathlib import Path
-    root = Path(__file__).resolve().parents[1]
-    csrc = root / "diffusion-llm-rs_amd" / "csrc"
-    lib = dllm._lib.LIB_PATH.parent
-    exe = tmp_path / "neighbors_host_check"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wno-option-ignored"]
-    cmd += [a for f in san for a in ("-Xarch_host", f)] + [san[0]]       # the last one links the runtimes
-    cmd += [f"-I{root / 'include'}", f"-I{csrc}", str(root / "tests" / "cpp" / "neighbors_host_check.cpp"),
-            str(csrc / "capi_host.cpp"), f"-L{lib}", "-ldllm_hip", f"-Wl,-rpath,{lib}", "-o", str(exe)]
-    subprocess.run(cmd, check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
-    assert " 0 failed" in r.stdout
+def test_host_entry_points_under_sanitizers(tmp_path):
+    """tests/cpp/neighbors_host_check.cpp (its own main) with csrc/host_rules.cpp and error.cpp, compiled by
+    g++ under the address and undefined-behaviour sanitizers (tests/host_check.py; no hipcc, no
+    library): exact-size heap buffers at every kind of dim, blocks from the start, middle and end."""
+    run_host_check("neighbors_host_check", tmp_path, timeout=120)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import search_ref as ref
+from tests.host_check import run_host_check
 
 # dim: one element; one group; a quarter trip; the trip edge from both sides and a strand's second
 # trip; a ragged second trip that is no multiple of 4 (rows then start at odd byte offsets); 768.
@@ -362,24 +363,8 @@ def test_vector_index_bookkeeping(dllm):
 
 # ---- the host entry points under the sanitizers -----------------------------------------------------------
 
-def test_host_entry_points_under_sanitizers(dllm, tmp_path):
-    """tests/cpp/search_host_check.cpp (its own main) with csrc/capi_host.cpp, both compiled for the
-    host under the address and undefined-behaviour sanitizers, the rest of the ABI from the built
-    library: exact-size heap buffers at every kind of dim, k beyond rows, an empty store."""
-    import os
-    import subprocess
-    from pathlib import Path
-    root = Path(__file__).resolve().parents[1]
-    csrc = root / "diffusion-llm-rs_amd" / "csrc"
-    lib = dllm._lib.LIB_PATH.parent
-    exe = tmp_path / "search_host_check"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wno-option-ignored"]
-    cmd += [a for f in san for a in ("-Xarch_host", f)] + [san[0]]       # the last one links the runtimes
-    cmd += [f"-I{root / 'include'}", f"-I{csrc}", str(root / "tests" / "cpp" / "search_host_check.cpp"),
-            str(csrc / "capi_host.cpp"), f"-L{lib}", "-ldllm_hip", f"-Wl,-rpath,{lib}", "-o", str(exe)]
-    subprocess.run(cmd, check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
-    assert " 0 failed" in r.stdout
+def test_host_entry_points_under_sanitizers(tmp_path):
+    """tests/cpp/search_host_check.cpp (its own main) with csrc/host_rules.cpp and error.cpp, compiled by
+    g++ under the address and undefined-behaviour sanitizers (tests/host_check.py; no hipcc, no
+    library): exact-size heap buffers at every kind of dim, k beyond rows, an empty store."""
+    run_host_check("search_host_check", tmp_path, timeout=120)

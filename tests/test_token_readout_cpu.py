@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from tests import token_ref as ref
+from tests.host_check import run_host_check
 
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "diffusion-llm-rs_amd" / "csrc"
@@ -242,23 +243,13 @@ def test_wrappers_exported(dllm):
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
-def test_host_entry_point_under_sanitizers(dllm, tmp_path):
-    """tests/cpp/token_host_check.cpp (its own main) with csrc/capi_host.cpp, both compiled for the
-    host under the address and undefined-behaviour sanitizers, the rest of the ABI from the built
-    library: exact-size heap buffers at every kind of V, both dtypes, padding that must not be read,
+def test_host_entry_point_under_sanitizers(tmp_path):
+    """tests/cpp/token_host_check.cpp (its own main) with csrc/host_rules.cpp and error.cpp, compiled by
+    g++ under the address and undefined-behaviour sanitizers (tests/host_check.py; no hipcc, no
+    library): exact-size heap buffers at every kind of V, both dtypes, padding that must not be read,
     the special rows, EXP's special points and a strided sample of its range."""
-    lib = dllm._lib.LIB_PATH.parent
-    exe = tmp_path / "token_host_check"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    cmd = [HIPCC, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wno-option-ignored"]
-    cmd += [a for f in san for a in ("-Xarch_host", f)] + [san[0]]       # the last one links the runtimes
-    cmd += [f"-I{ROOT / 'include'}", f"-I{CSRC}", str(ROOT / "tests" / "cpp" / "token_host_check.cpp"),
-            str(CSRC / "capi_host.cpp"), f"-L{lib}", "-ldllm_hip", f"-Wl,-rpath,{lib}", "-o", str(exe)]
-    subprocess.run(cmd, check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
-    assert " 0 failed" in r.stdout
+    run_host_check("token_host_check", tmp_path)
+
 
 
 def test_exp_exhaustive_sweep(tmp_path):
